@@ -12,11 +12,17 @@ loop body (crypto/crypto_test.go:103-131) over a batch.
 Before the W warmup steps the GPU runs the same step for --settle-ms of wall time (clock settle,
 DESIGN.md s5 "Clock ramp": after an idle start the clocks take ~70 ms of load to come up).
 
-At N = 1, after the headline, the same process also times the other BASELINE configs into
+A plain run does only what the headline needs: set up, settle, warm up, time the K steps, print the
+line.  `--full` adds everything else, as one run used to: the CPU baseline (config 1) before the GPU is
+touched, clock and power telemetry over the timed steps, the arena's golden digests after them, the
+copy kernel's rate for the roofline, and at N = 1, after the headline, the other BASELINE configs into
 `extra_configs` (never `value`): config 3 on the parity-checked workload (quantum_amd/workloads.py,
 with its golden arena digests), config 2 from pinned host memory (PCIe included) and config 5.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+`--dump-outputs DIR` writes what the last timed step left to DIR/<name>.npy (dump_outputs below); the
+inputs are seeded, so two builds run with the same arguments can be compared array for array.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no launcher starts torch.distributed.run with N ranks itself; under a
@@ -61,9 +67,15 @@ def parse() -> argparse.Namespace:
     p.add_argument("--settle-ms", type=float, default=500.0, help="clock settle before warmup (0 = none)")
     p.add_argument("--len", type=int, default=1350, help="payload bytes per packet")
     p.add_argument("--stride", type=int, default=0, help="slot stride (0 = smallest 64-B multiple)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extra", action="store_true", help="skip configs 3 / 5 and the host-memory rate (N=1)")
-    p.add_argument("--no-verify", action="store_true", help="skip the golden arena digests of configs 3 and 5")
+    p.add_argument("--full", action="store_true",
+                   help="also: the CPU baseline, the golden arena digests, clock / power telemetry, the copy "
+                        "kernel's rate for the roofline and (N=1) the other configs (extra_configs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step left (arena slots, status) to DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-extra", action="store_true",
+                   help="with --full: skip configs 3 / 5 and the host-memory rate (N=1)")
+    p.add_argument("--no-verify", action="store_true", help="with --full: skip the golden arena digests")
     p.add_argument("--cpu-threads", type=int, default=0, help="0 = the CPU share this job was given")
     p.add_argument("--dist-backend", default="nccl", help="nccl (RCCL, default) or gloo (rehearsal)")
     p.add_argument("--one-device", action="store_true",
@@ -1051,6 +1063,37 @@ def extra_per_packet(seconds: float = 1.5) -> dict:
     return out
 
 
+DUMP_SLOTS = 4096  # whole slots sampled by --dump-outputs, over all ranks
+DUMP_PREFIX = 1 << 20  # leading slots whose status and byte sums --dump-outputs writes, over all ranks
+
+
+def dump_outputs(out_dir: str, arena, status, stride: int, N: int, rank: int, world: int) -> dict:
+    """--dump-outputs: what a caller of the timed step holds after its last step, as float arrays (every
+    value a small integer, exact in float32 / float64).  The step seals and then opens in place, so the
+    arena is in the opened state: each slot's AAD and plaintext followed by the tag || nonce the seal
+    wrote -- the tag is GHASH over the slot's whole ciphertext, so a wrong sealed byte shows in it.
+      arena_slots.npy       float32 [S, stride]  S whole slots, a seeded sample (the same slots every run)
+      arena_slot_index.npy  float64 [S]          which slots those are
+      arena_slot_sums.npy   float64 [M]          the byte sum of each of the first M slots
+      status.npy            float32 [M]          the open's per-packet status (1 = authenticated)
+    S = 4096 / world and M = 2^20 / world slots per rank (capped by the rank's N): ~35 MB in all.  Rank r
+    > 0 writes <name>_rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    S, M = min(N, max(1, DUMP_SLOTS // world)), min(N, max(1, DUMP_PREFIX // world))
+    idx = np.sort(np.random.default_rng(0x5EED00D0 + rank).choice(N, S, replace=False))
+    slots = arena[:N * stride].view(N, stride)
+    arrays = {
+        "arena_slots": slots[torch.from_numpy(idx).to(arena.device)].cpu().numpy().astype(np.float32),
+        "arena_slot_index": idx.astype(np.float64),
+        "arena_slot_sums": slots[:M].sum(dim=1, dtype=torch.int64).cpu().numpy().astype(np.float64),
+        "status": status[:M].cpu().numpy().astype(np.float32),
+    }
+    suffix = f"_rank{rank}" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main() -> None:
     args = parse()
     launch_ranks(args)
@@ -1058,11 +1101,11 @@ def main() -> None:
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     key = derive_key(SECRET, SALT)  # crypto/aes.go:66, host, once
-    host = host_cpus()
+    host = host_cpus() if args.full else None
     # the CPU baseline first, before anything initialises the GPU (no runtime threads, no GPU-side
     # host work in this cgroup while the CPU chain runs)
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         print("[bench] cpu baseline sweep", file=sys.stderr, flush=True)
         cpu = cpu_baseline(key, args.len, args.cpu_threads or host["share"], host)
     dist = None
@@ -1118,8 +1161,10 @@ def main() -> None:
     # clock and power (GpuTelemetry): sampled from 100 ms into the settle loop (the clocks have come up
     # by then, DESIGN.md s5 "Clock ramp") through the timed steps -- the same step back to back all along,
     # so a short timed region (the driver's 20 steps are ~65 ms) still gets a few dozen samples
-    tele = GpuTelemetry(local)
-    tele.span = "the settle loop's last part, the warmup and the timed steps (the same step back to back)"
+    # (--full only: a plain run starts no sampling thread and reports None for the clock and the power)
+    tele = GpuTelemetry(local) if args.full else None
+    if tele is not None:
+        tele.span = "the settle loop's last part, the warmup and the timed steps (the same step back to back)"
     settle = 0
     t_settle = time.perf_counter()
     while (time.perf_counter() - t_settle) * 1e3 < args.settle_ms:
@@ -1127,9 +1172,10 @@ def main() -> None:
         settle += 1
         if settle % 8 == 0:
             torch.cuda.synchronize()  # bound the launch queue; the loop keeps the GPU busy
-            if not tele.started and (time.perf_counter() - t_settle) * 1e3 >= min(100.0, args.settle_ms / 2):
+            if (tele is not None and not tele.started
+                    and (time.perf_counter() - t_settle) * 1e3 >= min(100.0, args.settle_ms / 2)):
                 tele.start()
-    if not tele.started:
+    if tele is not None and not tele.started:
         tele.span = "the warmup and the timed steps"
         tele.start()
     for _ in range(args.warmup):
@@ -1148,10 +1194,16 @@ def main() -> None:
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    tele.stop()
-    clock = tele.summary()
-    tele.close()
+    if tele is not None:
+        tele.stop()
+        clock = tele.summary()
+        tele.close()
+    else:
+        clock = {"sclk_mhz_mean": None, "power_w_mean": None, "power_cap_w": None,
+                 "telemetry": "not sampled (--full samples the clock and the power)"}
     ok = int(status.sum().item()) == N  # the last timed open authenticated every packet
+    # the last timed step's outputs, before anything else touches the arena (untimed)
+    dumped = dump_outputs(args.dump_outputs, arena, status, stride, N, rank, world) if args.dump_outputs else None
     # max over ranks, AND of the per-rank status (the only cross-rank traffic; no data collective)
     seal_ms = sum(evs[2 * k].elapsed_time(evs[2 * k + 1]) for k in range(args.steps)) / args.steps
     open_ms = sum(evs[2 * k + 1].elapsed_time(evs[2 * k + 2]) for k in range(args.steps)) / args.steps
@@ -1159,7 +1211,11 @@ def main() -> None:
     coll_dev = dev if args.dist_backend == "nccl" else None
     elapsed, ok = shard.reduce_step_time(elapsed, ok, dist, coll_dev)
     # every rank checks its own arena against the golden (untimed, before anything else touches it)
-    digests = rank_digests(ctx, arena, nonces, status, stride, N, L, rank, stream, verify=not args.no_verify)
+    # (--full only: three hashes of up to 1.5 GB each through the host)
+    digests = rank_digests(ctx, arena, nonces, status, stride, N, L, rank, stream,
+                           verify=args.full and not args.no_verify)
+    if not args.full:
+        digests["digest_skipped"] = "not checked (--full checks the golden digests)"
 
     def flag(v):
         return -1.0 if v is None else float(bool(v))
@@ -1190,7 +1246,8 @@ def main() -> None:
     launches = -(-N // chunk)
     # after the timed region; an arena-sized buffer up to 4 GiB (past the 256-MiB Infinity Cache the rate
     # does not depend on the size: 6.52 / 6.47 TB/s at 1.48 / 8 GB, profiles/r6_s2)
-    copy_gbs = stream_copy_gbs(ctx, min(N * stride, 4 << 30), dev, stream)
+    # (--full only: a run of its own; a plain run quotes the roofline against the guide's copy figure)
+    copy_gbs = stream_copy_gbs(ctx, min(N * stride, 4 << 30), dev, stream) if args.full else None
 
     if rank == 0:
         line = {
@@ -1222,10 +1279,10 @@ def main() -> None:
                          "launch_ms": round(kms / launches, 4),
                          "achieved_read_only": round(achieved_read, 1),
                          "read_bytes_per_packet": read_pkt,
-                         "copy_achievable": round(copy_gbs, 1),
+                         "copy_achievable": round(copy_gbs, 1) if copy_gbs is not None else None,
                          "copy_reference_guide": COPY_GUIDE_GBS,
                          # against the larger of this run's copy kernel and the guide's measured float4 copy
-                         "frac_of_copy": round(achieved / max(copy_gbs, COPY_GUIDE_GBS), 4),
+                         "frac_of_copy": round(achieved / max(copy_gbs or 0.0, COPY_GUIDE_GBS), 4),
                          "binding_unit": "LDS (T-table AES + comb GHASH lookups, DESIGN.md 4.1)",
                          "lds_array_busy": lds_busy,
                          # the kernel's cycles per launch at the measured mean GFX clock: the box-independent
@@ -1245,7 +1302,10 @@ def main() -> None:
             **digests,
             "sclk_mhz_mean": clock["sclk_mhz_mean"], "power_w_mean": clock["power_w_mean"],
             "power_cap_w": clock["power_cap_w"], "gpu_clock_power": clock,
+            "full": args.full,
         }
+        if dumped is not None:
+            line["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         # every rank's digests: the line's flags are the AND over ranks (a rank without a golden prefix: None)
         for k in ("sealed_digest_ok", "opened_digest_ok"):
             flags = [g[k] for g in line["per_gpu"]]
@@ -1259,7 +1319,7 @@ def main() -> None:
         print(f"[bench] headline {line['value']} GiB/s", file=sys.stderr, flush=True)
         if cpu is not None:
             line["cpu_baseline"] = cpu
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             # the other BASELINE configs, timed after the headline in this process (never `value`)
             del arena_alloc, arena, nonces, status
             torch.cuda.empty_cache()

@@ -54,6 +54,42 @@ def test_telemetry_degrades_to_a_note():
     assert isinstance(s["telemetry"], str) and s["telemetry"]
 
 
+def test_dump_outputs_arrays(tmp_path):
+    """bench.dump_outputs on a host arena (no GPU needed): float arrays that hold the bytes exactly, the
+    same seeded slots on every call, rank r > 0 under its own names, and at the headline's size at most
+    64 MB in all."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import bench
+
+    n, stride = 5000, 96
+    rng = np.random.default_rng(7)
+    host = rng.integers(0, 256, n * stride + 4, dtype=np.uint8)
+    arena, status = torch.from_numpy(host), torch.ones(n, dtype=torch.uint8)
+    status[17] = 0
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arena, status, stride, n, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), arena, status, stride, n, 0, 1)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in shapes}
+    for k, a in got.items():
+        assert a.dtype in (np.float32, np.float64) and list(a.shape) == shapes[k]
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{k}.npy"))
+    slots = host[:n * stride].reshape(n, stride)
+    idx = got["arena_slot_index"].astype(np.int64)
+    assert len(idx) == min(n, bench.DUMP_SLOTS) and len(set(idx.tolist())) == len(idx)
+    assert np.array_equal(got["arena_slots"], slots[idx].astype(np.float32))
+    assert np.array_equal(got["arena_slot_sums"], slots.sum(axis=1, dtype=np.int64).astype(np.float64))
+    assert np.array_equal(got["status"], status.numpy().astype(np.float32))
+    # two ranks: half the slots each, other slots for rank 1, suffixed names
+    bench.dump_outputs(str(tmp_path / "a"), arena, status, stride, n, 1, 2)
+    idx1 = np.load(tmp_path / "a" / "arena_slot_index_rank1.npy")
+    assert len(idx1) == bench.DUMP_SLOTS // 2 and not np.array_equal(idx1, idx[:len(idx1)])
+    # the headline's layout (2^20 slots of 1408 B): bytes written, from the shapes alone
+    S, M = bench.DUMP_SLOTS, bench.DUMP_PREFIX
+    assert 4 * S * 1408 + 8 * S + 8 * M + 4 * M <= 64 * 10**6
+
+
 def test_rank_digests_skip_other_layouts():
     """bench.rank_digests checks only the layout tests/golden/rank_digest.json was made for (L 1350,
     stride 1408, ranks 0-7, at least 2^16 slots); anything else says why it was skipped (no GPU needed)."""

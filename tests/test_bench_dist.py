@@ -34,7 +34,7 @@ def test_bench_two_ranks_one_device():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", "29533", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "3", "--warmup", "1", "--packets", "65536", "--dist-backend", "gloo",
-           "--one-device"]
+           "--one-device", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -62,7 +62,7 @@ def test_bench_config4_two_ranks_one_device():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", "29534", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--settle-ms", "0", "--dist-backend", "gloo",
-           "--one-device"]
+           "--one-device", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -87,7 +87,7 @@ def test_bench_rccl_process_group_one_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", "29535", os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--steps", "3", "--warmup", "1", "--packets", "65536", "--settle-ms", "0",
-           "--no-extra", "--no-cpu-baseline"]
+           "--full", "--no-extra", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -130,7 +130,7 @@ def test_bench_eight_ranks_one_device():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
            "--master-addr", "127.0.0.1", "--master-port", "29536", os.path.join(ROOT, "bench.py"),
            "--gpus", "8", "--steps", "3", "--warmup", "1", "--packets", "262144", "--settle-ms", "0",
-           "--dist-backend", "gloo", "--one-device"]
+           "--dist-backend", "gloo", "--one-device", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -25,10 +25,10 @@ for s in $STEPS; do
       timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       check smoke $? ;;
     bench)
-      timeout -k 10 600 python3 bench.py > $OUT/bench_line.json 2> $OUT/bench.err
+      timeout -k 10 600 python3 bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
       check bench $? ;;
     benchdrv)  # the driver's round-end arguments (BENCH_r05: --steps 20 --warmup 5)
-      timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_drv_line.json 2> $OUT/bench_drv.err
+      timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 --full > $OUT/bench_drv_line.json 2> $OUT/bench_drv.err
       check benchdrv $? ;;
     ab)
       timeout -k 10 300 python3 tools/ab_libs.py ablib/libqgcm_r2.so quantum_amd/libqgcm.so --rounds 15 > $OUT/ab.txt 2>&1
