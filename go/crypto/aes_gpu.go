@@ -30,7 +30,11 @@
 //   - Encrypt with length < 0 or len(data) < length + 28 returns (-1, errShortBuffer);
 //   - Decrypt of fewer than 28 bytes returns errOpen (the reference panics below 12 bytes,
 //     crypto/aes.go:58-59, and returns errOpen from 12 to 27);
-//   - additional data longer than 4 bytes (the Payload IP header; quantum never passes more) is refused.
+//   - additional data may have any length up to QGCM_MAX_AAD (16384 bytes), as with cipher.AEAD, while
+//     record and additional data fit libqgcm's per-packet engine together (qgcm.h, qgcm_seal_one):
+//     ((4 + length + 28 + 15) &^ 15) + ((len(additional) + 15) &^ 15) <= 32752, which every packet
+//     quantum can produce does many times over.  Beyond that Encrypt returns (-1, an error) with data
+//     untouched and Decrypt returns errOpen.
 // nil or empty `additional` (crypto/crypto_test.go TestAES passes nil) and empty slices never have
 // their first element addressed: bytePtr returns nil for them.
 package crypto
@@ -64,7 +68,6 @@ var (
 	// errOpen is the error cipher.AEAD.Open returns on a tag mismatch (crypto/cipher gcm.go).
 	errOpen        = errors.New("cipher: message authentication failed")
 	errShortBuffer = errors.New("qgcm: data buffer shorter than length + 28")
-	errAdditional  = errors.New("qgcm: additional data longer than 4 bytes")
 	errSlots       = errors.New("qgcm: out of key slots (QGCM_MAX_PEERS)")
 	errBatch       = errors.New("qgcm: batch record outside the arena, or status shorter than the batch")
 )
@@ -103,13 +106,11 @@ func (crypt *AES) DecryptedSize(data []byte) int { return len(data) - overhead }
 // ciphertext, then the 16-byte tag and the 12-byte nonce (drawn by libqgcm from getrandom(2),
 // crypto/rand's source); returns length + 28.
 //
-// additional may be nil.
+// additional may be nil, and may have any length within the size rule in this file's header note (the
+// C call returns -1 beyond it, reported as the seal error).
 func (crypt *AES) Encrypt(data []byte, length int, additional []byte) (int, error) {
 	if length < 0 || length+overhead > len(data) {
 		return -1, errShortBuffer
-	}
-	if len(additional) > 4 {
-		return -1, errAdditional
 	}
 	n := C.qgcm_seal_one(crypt.ctx, C.uint32_t(crypt.idx), bytePtr(data), C.long(length), bytePtr(additional),
 		C.uint32_t(len(additional)), nil)
@@ -126,7 +127,7 @@ func (crypt *AES) Encrypt(data []byte, length int, additional []byte) (int, erro
 //
 // additional and data must be the same buffers passed to Encrypt.
 func (crypt *AES) Decrypt(data []byte, additional []byte) (int, error) {
-	if len(data) < overhead || len(additional) > 4 {
+	if len(data) < overhead {
 		return crypt.DecryptedSize(data), errOpen
 	}
 	n := C.qgcm_open_one(crypt.ctx, C.uint32_t(crypt.idx), bytePtr(data), C.long(len(data)), bytePtr(additional),

@@ -46,6 +46,7 @@ extern "C" {
 #define QGCM_PBKDF2_ITERS 10000 /* crypto/aes.go:18 */
 #define QGCM_MAX_PAYLOAD (1u << 28) /* largest plaintext per packet (GCM allows 2^36-32; packets are <= 9000) */
 #define QGCM_ERRLEN 120      /* crypto/dtls.go:23 errorLen */
+#define QGCM_MAX_AAD 16384   /* longest additional data of a per-packet call (qgcm_seal_one / qgcm_open_one) */
 #define QGCM_MAX_BATCH (1u << 31) /* packets per batch call (tile indices stay 32-bit); more -> QGCM_E_ARG */
 /* largest max_keys of a context: the descriptor sort key is key_idx << 12 | length rank, 32 bits, and
  * its all-ones value marks excluded packets, so key index 2^20 - 1 is reserved */
@@ -126,11 +127,22 @@ int qgcm_open_uniform(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t
 /* ---- per-packet host calls, the exact Encrypt/Decrypt contract ---- */
 /* crypto/aes.go:41-52: seals data[0:length] in place, appends tag and nonce; data must have
  * capacity length+28.  nonce NULL -> 12 fresh bytes from getrandom(2) as crypto/rand does.
- * aad may be NULL (aad_len 0).  Returns length+28, or -1. */
+ * aad may be NULL (aad_len 0); aad_len may be anything in [0, QGCM_MAX_AAD], as cipher.AEAD takes
+ * additional data of any length.  Calls with aad_len <= 4 (nil, or the Payload IP header) are served
+ * on every path, payloads that fall through to the batch kernel included.  Calls with aad_len > 4
+ * are served by the latency engine alone, when the record and the additional data fit its staging
+ * area together:
+ *   ((4 + length + 28 + 15) & ~15) + ((aad_len + 15) & ~15) <= 32752
+ * (every packet quantum can produce fits this many times over).  Anything larger returns -1 and leaves
+ * data untouched; so does every aad_len > 4 on a context created with QGCM_ONE_KERNEL=0 (that A/B knob
+ * forces the batch kernel, which has no long-AAD form).  Returns length+28, or -1. */
 long qgcm_seal_one(qgcm_ctx *ctx, uint32_t key_idx, uint8_t *data, long length, const uint8_t *aad,
                    uint32_t aad_len, const uint8_t *nonce);
 /* crypto/aes.go:57-62: opens data[0:len] in place.  Returns len-28, or -1 (errOpen; data[0:len-28]
- * zeroed on tag mismatch; len < 28 leaves data untouched -- the reference panics below 12). */
+ * zeroed on tag mismatch; len < 28 leaves data untouched -- the reference panics below 12).
+ * aad_len as for qgcm_seal_one: [0, QGCM_MAX_AAD]; beyond 4 bytes the call is served when
+ *   ((4 + len + 15) & ~15) + ((aad_len + 15) & ~15) <= 32752
+ * and the context was not created with QGCM_ONE_KERNEL=0, else it returns -1 with data untouched. */
 long qgcm_open_one(qgcm_ctx *ctx, uint32_t key_idx, uint8_t *data, long len, const uint8_t *aad,
                    uint32_t aad_len);
 

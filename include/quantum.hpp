@@ -138,7 +138,8 @@ class AES {
     int EncryptedSize(common::Slice data) const { return (int)data.len + Overhead + NonceSize; }  // :29-31
     int DecryptedSize(common::Slice data) const { return (int)data.len - Overhead - NonceSize; }  // :34-36
     // crypto/aes.go:41-52: seals data[0:length] in place with a fresh random nonce, appends tag and
-    // nonce; data needs capacity length + 28.  additional may be empty (nil).
+    // nonce; data needs capacity length + 28.  additional may be empty (nil) or of any length
+    // up to QGCM_MAX_AAD (past 4 bytes: while it fits qgcm_seal_one's size rule, qgcm.h).
     virtual std::pair<int, Error> Encrypt(common::Slice data, int length, common::Slice additional) const;
     // crypto/aes.go:57-62: opens data in place (nonce = last 12 B, tag the 16 before), returns
     // len - 28; on authentication failure the plaintext region is zeroed (Go 1.9 gcm.Open).

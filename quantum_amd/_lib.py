@@ -43,6 +43,7 @@ QGCM_E_KEY = -3
 QGCM_E_AUTH = -4
 QGCM_E_NOMEM = -5
 OVERHEAD = 28
+QGCM_MAX_AAD = 16384  # longest additional data of a per-packet call (qgcm_seal_one / qgcm_open_one)
 ERRLEN = 120
 
 

@@ -24,6 +24,7 @@ iterations = 10000
 keyLength = 32
 NonceSize = 12
 Overhead = 16
+MaxAdditional = _lib.QGCM_MAX_AAD  # longest `additional` of Encrypt / Decrypt (qgcm.h QGCM_MAX_AAD)
 
 
 class ErrOpen(Exception):
@@ -189,6 +190,9 @@ class AES:
 
     def Encrypt(self, data, length: int, additional=None, nonce: bytes | None = None):
         """crypto/aes.go:41-52.  Seals data[:length] in place; tag then nonce follow it.
+        `additional` may have any length up to MaxAdditional, as with cipher.AEAD; past 4 bytes it is
+        served while record and additional data fit the per-packet engine together (qgcm.h,
+        qgcm_seal_one), else the call returns an error with data untouched.
         `nonce` is an injection point for parity tests (the reference always draws it)."""
         addr, cap, keep = _addr(data)
         if length < 0 or length + Overhead + NonceSize > cap:
@@ -201,7 +205,8 @@ class AES:
         return n, None
 
     def Decrypt(self, data, additional=None):
-        """crypto/aes.go:57-62.  Opens data in place; returns (DecryptedSize(data), err)."""
+        """crypto/aes.go:57-62.  Opens data in place; returns (DecryptedSize(data), err).  `additional`
+        as for Encrypt (past the size rule: ErrOpen, data untouched)."""
         addr, length, keep = _addr(data)
         if length < NonceSize:
             raise IndexError("slice bounds out of range")  # the reference panics (negative slice)

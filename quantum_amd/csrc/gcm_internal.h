@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/qgcm.h"
+#include "one_fit.h"
 
 namespace qgcm {
 
@@ -42,7 +43,8 @@ struct Batch {
     uint32_t uniform_key;
     uint32_t n;
     uint32_t n_items;           // multiple of 64
-    uint32_t aad_len;           // 0 or 4
+    uint32_t aad_len;           // 0..4 for batches; up to QGCM_MAX_AAD for a per-packet call (gcm_one_kernel, n = 1:
+                                // beyond 4 the bytes follow the record as a tail, one_fit.h)
     uint32_t max_keys;
     uint32_t *tile_counter;     // descriptor quad kernels: dynamic tile index (zeroed per launch)
     const uint32_t *tile_keys;  // descriptor quad kernels: key of each 16-entry tile (all ones: padding,
@@ -111,8 +113,8 @@ hipError_t launch_quad_worklist(const qgcm_desc *descs, uint32_t n, uint32_t max
 bool small_worklist(uint32_t n, bool on);
 hipError_t launch_packets(bool seal, int variant, const Batch &b, int grid, hipStream_t s);
 // One packet, one 512-thread workgroup (qgcm_seal_one / qgcm_open_one): the slot (b.stride bytes,
-// a multiple of 16, at most kOneCap - 16) is staged in LDS; b.n must be 1.
-constexpr uint32_t kOneCap = 32768;
+// a multiple of 16) and, for b.aad_len > 4, the tail of additional data behind it (one_fit.h; kOneCap:
+// together at most kOneCap - 16) are staged in LDS; b.n must be 1.
 hipError_t launch_one(bool seal, const Batch &b, hipStream_t s);
 
 // Resident per-packet service (resident.cpp): `workers` 512-thread workgroups of gcm_one_kernel's
@@ -120,8 +122,10 @@ hipError_t launch_one(bool seal, const Batch &b, hipStream_t s);
 // Slot s belongs to worker s / per_worker.  Requests travel in DEVICE memory (fine-grained, which the
 // host CPU writes through the BAR: posted writes, and the GPU polls and reads its own HBM); results
 // travel in pinned host memory (the GPU's posted writes, which the host reads from its cache).
-// Host -> device: the slot's input bytes into in[s], then req[s].y..w = {op (1 seal, 0 open) |
-// aad_len << 1, len, key_idx}, then req[s].x = seq (31-bit, +1 per request), each step fenced
+// Host -> device: the slot's input bytes into in[s] (additional data longer than 4 B as a tail of 16-B
+// rows behind the 16-B-rounded record, its padding zeroed), then req[s].y..w = {op (bit 0: 1 seal,
+// 0 open) | announce << 8 (a seal that leaves the slot's next nonce in its last 16 B) | aad_len << 16,
+// len, key_idx}, then req[s].x = seq (31-bit, +1 per request), each step fenced
 // (sfence: the write-combined stores land in that order).  stop[16 w] != 0 ends worker w.
 // Device -> host: the result bytes into out[s], then done[s] = seq << 1 | verdict.  Every access of
 // memory the other side writes goes around the GPU caches (16-B sc0 sc1 buffer accesses, system-scope
@@ -129,7 +133,7 @@ hipError_t launch_one(bool seal, const Batch &b, hipStream_t s);
 // served for idle_ticks or the instance is life_ticks old (100 MHz clock): it raises the device
 // shutdown word, every worker serves what its records hold and leaves, and the last one writes
 // *over = gen.
-constexpr uint32_t kResSlotBytes = 16384;  // request slot: [aad 4][payload][tag 16][nonce 12], 16-B rounded
+// request slot (kResSlotBytes, one_fit.h): [aad 4][payload][tag 16][nonce 12], 16-B rounded, [aad tail]
 constexpr uint32_t kResMaxPerWorker = 64;
 constexpr size_t kResDevBytes = 64;        // device control words: [0] last activity, [1] shutdown, [2] left
 struct ResArgs {

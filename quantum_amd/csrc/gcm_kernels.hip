@@ -1217,6 +1217,11 @@ extern "C" int qgcm_debug_seg_stats(unsigned long long *out, int n, int reset) {
 // DESIGN.md 4.3 has the device-side timeline of each step.
 // LDS: [0, 64K) Te, [64K, 120K) comb tables of H^(2^l), [120K, 120K + kOneCap) the slot at +12
 // (payload 16-B aligned), 64 B of scratch (E_K(J0), the GHASH value), 2 KiB of GHASH exchange.
+// Additional data longer than the record's 4 bytes (per-packet calls only) follows the 16-B-rounded
+// record as a tail of ceil(aad_len / 16) rows, staged by the same pass: the tail starts on a row
+// boundary of the slot (so the fit rule is plain row counts, one_fit.h), which puts AAD block i at
+// kOneBuf + 12 + 16 (n16 + i), 12 mod 16 -- read as four lds32 like row(), not one lds128.  The
+// record's first word is then zero and no part of the hash.  Only the record's n16 rows are written back.
 constexpr uint32_t kOneThreads = 512;
 constexpr uint32_t kOneTabs = 7;
 constexpr uint32_t kOneBuf = kTeBytes + kOneTabs * kGhBytes;
@@ -1417,12 +1422,15 @@ __device__ __forceinline__ void ks_fill(const uint32_t *__restrict__ rk_table, u
 // comb tables of H^(2^l) that this packet needs beyond what `tab_key` / `tab_n` say is loaded (both
 // workgroup-uniform, updated here; a caller serving several packets puts a workgroup barrier
 // between two calls).  The slot (16-B aligned, (4 + Lin (+ 28 for seal) + 15) & ~15
-// bytes, checked by the caller) is staged in LDS, sealed or opened there and written back whole.
+// bytes, plus (aad_len + 15) & ~15 bytes of additional data behind it when aad_len > 4; checked by the
+// caller) is staged in LDS, sealed or opened there and the record written back whole.
 // nonce: seal only, 12 B, or NULL for the nonce already in the slot.  ks_tag / ks_lds (seal, resident
 // kernel): a keystream computed ahead (ks_fill), used when its tag names this key and nonce.  Returns
 // the verdict (bit 0: 1 ok, 0 authentication failure; bit 1: the keystream ahead was used), the same
 // on every thread.
-template <bool kSeal, bool kSys>
+// kLong: additional data past 4 bytes (the tail); a compile-time fork, so the 4-byte form every packet of
+// the tunnel takes carries none of the tail's code (the callers branch on aad_len, workgroup-uniform).
+template <bool kSeal, bool kSys, bool kLong>
 __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_table, const uint8_t *in, uint8_t *out,
                                uint32_t Lin,
                                uint32_t key, uint32_t aad_len, const uint8_t *nonce, bool fill_te, uint32_t &tab_key,
@@ -1432,12 +1440,15 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
     const uint32_t n16 = (uint32_t)((4ull + Lin + (kSeal ? QGCM_OVERHEAD : 0) + 15) >> 4);
     const uint32_t L = kSeal ? Lin : Lin - QGCM_OVERHEAD;
     const uint32_t A = kOneBuf + 12u, P = kOneBuf + 16u;  // slot base (AAD), payload base
+    // additional data: na GHASH blocks -- one from the record's first word (aad_len <= 4), else the
+    // rows of the tail behind the record; nst rows are staged, n16 written back (workgroup-uniform)
+    const uint32_t na = kLong ? one_aad_blocks(aad_len) : 1u, nst = kLong ? n16 + one_tail_rows(aad_len) : n16;
     // 1. stage the slot: every load issued before the table fill, so the PCIe round trip overlaps it
     uint4 v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const uint32_t i = tid + k * kOneThreads;
-        if (i < n16) v[k] = slot_ld16<kSys>(in, i);
+        if (i < nst) v[k] = slot_ld16<kSys>(in, i);
     }
     // the column-sliced counter blocks' round keys, before the table reads (see ColKeys)
     const Keys kk = {rk_table + (size_t)key * kRkWords, rk_table + (size_t)key * kRkWords + 64};
@@ -1446,11 +1457,11 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
     if (sliced) col_keys(kk, tid & 3u, ck);
     // The table fills load everything first and store after (one memory latency, not one per
     // iteration): Te0/Te1 words for 32 replicas per row, then the comb tables of H^(2^l) -- only the
-    // ones this packet's GHASH reads (H^(2^l) for the Estrin levels up to bit-length(min(d + 2, 63)),
+    // ones this packet's GHASH reads (H^(2^l) for the Estrin levels up to bit-length(min(emax, 63)),
     // H^64 once a chain owns two exponents) and not loaded yet for this key.
     constexpr int kGhIt = kOneTabs * 512 / kOneThreads;  // 7
     const uint4 *gh = b.gh_table + (size_t)key * kGhEntries;
-    const uint32_t emax = ((L + 15u) >> 4) + 2u;  // GHASH exponents 1 .. d + 2 (step 3)
+    const uint32_t emax = ((L + 15u) >> 4) + 1u + na;  // GHASH exponents 1 .. d + 1 + na (step 3)
     // flat GHASH (step 3) from the key's global tables of H^1 .. H^kPwPowers: no comb tables in LDS
     const bool flat = b.pw_table != nullptr && key < b.pw_keys && emax <= kPwPowers;  // workgroup-uniform
     const uint32_t ntabs = flat ? 0u : emax >= 64u ? kOneTabs : 32u - __builtin_clz(emax);
@@ -1475,7 +1486,7 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const uint32_t i = tid + k * kOneThreads;
-        if (i < n16) {
+        if (i < nst) {
             const uint32_t a = A + 16 * i;
             lds_st32(a, v[k].x);
             lds_st32(a + 4, v[k].y);
@@ -1483,7 +1494,7 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
             lds_st32(a + 12, v[k].w);
         }
     }
-    for (uint32_t i = tid + 4 * kOneThreads; i < n16; i += kOneThreads) {  // slots over 16 KiB
+    for (uint32_t i = tid + 4 * kOneThreads; i < nst; i += kOneThreads) {  // past the 4 x 512 unrolled rows
         const uint4 w = slot_ld16<kSys>(in, i);
         const uint32_t a = A + 16 * i;
         lds_st32(a, w.x);
@@ -1513,7 +1524,8 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
     uint32_t m0, m1, m2, m3;
     block_mask(r, m0, m1, m2, m3);
     // a seal whose nonce's keystream a resident worker computed ahead (ks_tag: {key + 1, nonce} in LDS,
-    // ks_lds: the blocks; see ks_fill); flat packets have d + 2 <= kPwPowers, so d < kKsBlocks - 1
+    // ks_lds: the blocks; see ks_fill); flat packets have d + 1 + na <= kPwPowers with na >= 1, so
+    // d < kKsBlocks - 1
     const bool use_ks = kSeal && ks_tag && flat && lds32(ks_tag) == key + 1u && lds32(ks_tag + 4) == n0 &&
                         lds32(ks_tag + 8) == n1 && lds32(ks_tag + 12) == n2;  // workgroup-uniform
 
@@ -1566,10 +1578,23 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
     // Y = sum_i B_i H^(N+1-i) is c + 2 mod 64 (the AAD block included): a Horner chain by H^64, then
     // sum_c Z_c H^c by radix-2 Estrin levels (multiply by H^(2^l), add chain c + 2^l's product through
     // LDS), then Y = S H^2 + [len(A)]||[len(C)] H.  Every thread calls it (it has workgroup barriers).
-    // the block of GHASH exponent ex in Y = sum_ex B_ex H^ex: the AAD block (ex = d + 2), the length
-    // block (ex = 1), else ciphertext block d + 1 - ex (the partial one masked)
+    // the block of GHASH exponent ex (1 .. emax) in Y = sum_ex B_ex H^ex, for both GHASH forms: AAD
+    // block i at ex = emax - i (up to 4 bytes: the one block from the record's first word, ex = d + 2;
+    // longer: row i of the tail, the last one masked by aad_len so that stale bytes of a reused slot never
+    // enter the hash), the length block (ex = 1), else ciphertext block d + 1 - ex (the partial one masked)
     auto gblock = [&](uint32_t ex) {
-        if (ex == d + 2u) return uint4{aad_len ? lds32(A) & (aad_len >= 4 ? 0xffffffffu : lowmask(aad_len)) : 0u, 0u, 0u, 0u};
+        if constexpr (!kLong) {
+            if (ex == d + 2u) return uint4{aad_len ? lds32(A) & (aad_len >= 4 ? 0xffffffffu : lowmask(aad_len)) : 0u, 0u, 0u, 0u};
+        } else if (ex > d + 1u) {
+            const uint32_t i = emax - ex, ta = A + 16u * (n16 + i);
+            uint4 ab{lds32(ta), lds32(ta + 4), lds32(ta + 8), lds32(ta + 12)};
+            if (i == na - 1u && (aad_len & 15u)) {
+                uint32_t a0, a1, a2, a3;
+                block_mask(aad_len & 15u, a0, a1, a2, a3);
+                ab = uint4{ab.x & a0, ab.y & a1, ab.z & a2, ab.w & a3};
+            }
+            return ab;
+        }
         if (ex == 1) return uint4{0u, bswap(aad_len * 8u), 0u, bswap(L * 8u)};
         const uint32_t bi = d + 1u - ex;
         uint4 cb = lds128(P + 16 * bi);
@@ -1581,7 +1606,7 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
         }
         return cb;
     };
-    // Flat GHASH for packets with d + 2 <= kPwPowers exponents: every product B_ex H^ex is independent,
+    // Flat GHASH for packets with emax = d + 1 + na <= kPwPowers exponents: every product B_ex H^ex is independent,
     // looked up in the key's kPwBits-bit comb table of H^ex (global memory, pw_setup_kernel): chain c's
     // 8 lanes take ex = c + 1 and c + 65, lane e the windows e, e + 8, ... of the block (bits of the
     // GHASH bit stream, x^0 first).  One round of independent table reads replaces the Horner step and
@@ -1658,30 +1683,16 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
         if (flat) return flat_finish();
         const uint32_t c = tid >> 3, e = tid & 7u;
         uint32_t z0 = 0, z1 = 0, z2 = 0, z3 = 0;
-        // Exponents 1 (the length block) .. d + 2 (the AAD block; zero without additional data), so
-        // Y = sum_c Z_c H^c with no multiply after the tree.  Chain c's exponents e = c (mod 64), highest
-        // first (chain-uniform loop); chain 0's lowest is 64, hence its one more multiply by H^64.
-        const uint32_t emax = d + 2u;
+        // Exponents 1 (the length block) .. emax = d + 1 + na (the first AAD block; one zero block without
+        // additional data), so Y = sum_c Z_c H^c with no multiply after the tree.  Chain c's exponents
+        // e = c (mod 64), highest first (chain-uniform loop); chain 0's lowest is 64, hence its one more
+        // multiply by H^64.
         const uint32_t ehi = c == 0 ? (emax & ~63u) : (c <= emax ? c + ((emax - c) & ~63u) : 0u);
         const uint32_t elo = c ? c : 64u;
         const uint32_t steps = ehi >= elo ? (ehi - elo) / 64u + 1u : 0u;  // ehi = 0: none
         for (uint32_t k = 0; k < steps; ++k) {
             const uint32_t ex = ehi - 64u * k;
-            uint4 cb;
-            if (ex == emax) {  // the additional data
-                cb = uint4{aad_len ? lds32(A) & (aad_len >= 4 ? 0xffffffffu : lowmask(aad_len)) : 0u, 0u, 0u, 0u};
-            } else if (ex == 1) {  // [len(A)]_64 || [len(C)]_64 in bits
-                cb = uint4{0u, bswap(aad_len * 8u), 0u, bswap(L * 8u)};
-            } else {  // ciphertext block d + 1 - ex
-                const uint32_t bi = d + 1u - ex;
-                cb = lds128(P + 16 * bi);
-                if (bi == nfull) {
-                    cb.x &= m0;
-                    cb.y &= m1;
-                    cb.z &= m2;
-                    cb.w &= m3;
-                }
-            }
+            const uint4 cb = gblock(ex);
             if (k) ghash_mul8(z0, z1, z2, z3, kTeBytes + 6 * kGhBytes, e);  // H^64
             z0 ^= cb.x;
             z1 ^= cb.y;
@@ -1819,7 +1830,8 @@ __device__ uint32_t one_packet(const Batch &b, const uint32_t *__restrict__ rk_t
 
 // One workgroup per packet: slot i at b.arena + i * b.stride, b.uniform_len = L (seal) or L + 28
 // (open), b.uniform_key (a per-packet call is a batch of one).  Slots are 16-B aligned and
-// (4 + len (+ 28 for seal) + 15) & ~15 bytes long, at most kOneCap - 16; seal nonces come from
+// (4 + len (+ 28 for seal) + 15) & ~15 bytes long, at most kOneCap - 16 (a per-packet call, b.n = 1,
+// with b.aad_len > 4: the tail of additional data behind the slot included); seal nonces come from
 // b.nonces (12 B per packet) when it is set, else from the slot.  b.status[packet] = verdict.
 // With b.descs set (small keyed batches, run_descs_one), packet i is descs[i] instead: its record
 // at a 16-B-aligned offset, no other record inside its 16-B-rounded staging area.
@@ -1837,9 +1849,14 @@ __global__ void __launch_bounds__(kOneThreads) gcm_one_kernel(Batch b, const uin
     }
     const uint32_t n16 = (uint32_t)((4ull + Lin + (kSeal ? QGCM_OVERHEAD : 0) + 15) >> 4);
     // as the batch kernels: a key index out of range or an open shorter than 28 B fails the packet
-    // (slot untouched); so does a slot past the LDS staging area or misaligned (the host never sends one)
+    // (slot untouched); so does a slot past the LDS staging area or misaligned, and additional data past 4
+    // bytes on anything but a lone uniform packet whose record and tail fit the staging area together
+    // (the host never sends one)
+    const bool long_aad = b.aad_len > 4u;
     if (key >= b.max_keys || !b.key_valid[key] || (!kSeal && Lin < (uint32_t)QGCM_OVERHEAD) || Lin >= kOneCap ||
-        n16 * 16u > kOneCap - 16u || (off & 15u)) {
+        n16 * 16u > kOneCap - 16u || (off & 15u) ||
+        (long_aad && (b.n != 1u || b.descs || b.aad_len > (uint32_t)QGCM_MAX_AAD ||
+                      (n16 + one_tail_rows(b.aad_len)) * 16u > kOneCap - 16u))) {
         if (tid == 0) {
             if (b.status) b.status[pkt] = 0;
             if (b.done) {  // the host waits on the flag
@@ -1850,9 +1867,12 @@ __global__ void __launch_bounds__(kOneThreads) gcm_one_kernel(Batch b, const uin
         return;
     }
     uint32_t tab_key = 0xffffffffu, tab_n = 0;
-    const uint32_t ok = one_packet<kSeal, false>(b, rk_table, b.arena + off, b.arena + off, Lin, key, b.aad_len,
-                                                 kSeal && b.nonces ? b.nonces + 12ull * pkt : nullptr, true, tab_key,
-                                                 tab_n);
+    const uint8_t *const np = kSeal && b.nonces ? b.nonces + 12ull * pkt : nullptr;
+    const uint32_t ok =
+        long_aad ? one_packet<kSeal, false, true>(b, rk_table, b.arena + off, b.arena + off, Lin, key, b.aad_len, np, true,
+                                                  tab_key, tab_n)
+                 : one_packet<kSeal, false, false>(b, rk_table, b.arena + off, b.arena + off, Lin, key, b.aad_len, np,
+                                                   true, tab_key, tab_n);
     if (tid == 0 && b.status) b.status[pkt] = ok;
     if (b.done) {  // completion flag: every thread's stores reach the system before thread 0 sets it
         __threadfence_system();
@@ -1989,12 +2009,13 @@ __global__ void __launch_bounds__(kOneThreads) gcm_resident_kernel(Batch b, cons
             mask &= mask - 1;
             const uint32_t sl = first + j;
             const uint4 m = lds128(kResRec + 16 * j);
-            const uint32_t q = m.x & 0x7fffffffu, op = m.y & 1u, aad = (m.y >> 1) & 0x7fu, Lin = m.z, key = m.w;
+            const uint32_t q = m.x & 0x7fffffffu, op = m.y & 1u, aad = m.y >> 16, Lin = m.z, key = m.w;
             const bool ahead = (m.y >> 8) & 1u;  // a seal that announces the slot's next nonce
-            const uint64_t stage = (4ull + Lin + (op ? QGCM_OVERHEAD : 0) + 15) & ~15ull;
-            const bool valid = aad <= 4u && key < b.max_keys && b.key_valid[key] &&
+            // as resident_call: record and tail of additional data fit the slot (short of the announced
+            // nonce's row) and the LDS staging area
+            const bool valid = key < b.max_keys && b.key_valid[key] &&
                                (op ? Lin < QGCM_MAX_PAYLOAD : Lin >= (uint32_t)QGCM_OVERHEAD) &&
-                               stage <= kResSlotBytes && stage <= kOneCap - 16;
+                               one_fits_resident(Lin, op != 0u, aad, ahead);
             uint32_t ok = 0;
             const uint8_t *in = a.in + (size_t)sl * kResSlotBytes;
             uint8_t *out = a.out + (size_t)sl * kResSlotBytes;
@@ -2003,10 +2024,16 @@ __global__ void __launch_bounds__(kOneThreads) gcm_resident_kernel(Batch b, cons
             uint4 nn{0, 0, 0, 0};
             if (announce && tid == 0) nn = host_ld16(in, kResSlotBytes, kResSlotBytes - 16);
             const uint32_t kt = op && j < nks ? kResKs + 16 * j : 0u;
-            if (valid)
-                ok = op ? one_packet<true, true>(b, rk_table, in, out, Lin, key, aad, nullptr, false, tab_key, tab_n, kt,
-                                                 kTeBytes + kKsBytes * j)
-                        : one_packet<false, true>(b, rk_table, in, out, Lin, key, aad, nullptr, false, tab_key, tab_n);
+            if (valid && aad <= 4u)
+                ok = op ? one_packet<true, true, false>(b, rk_table, in, out, Lin, key, aad, nullptr, false, tab_key, tab_n,
+                                                        kt, kTeBytes + kKsBytes * j)
+                        : one_packet<false, true, false>(b, rk_table, in, out, Lin, key, aad, nullptr, false, tab_key,
+                                                         tab_n);
+            else if (valid)  // additional data past 4 bytes: the form with the tail
+                ok = op ? one_packet<true, true, true>(b, rk_table, in, out, Lin, key, aad, nullptr, false, tab_key, tab_n,
+                                                       kt, kTeBytes + kKsBytes * j)
+                        : one_packet<false, true, true>(b, rk_table, in, out, Lin, key, aad, nullptr, false, tab_key,
+                                                        tab_n);
             const bool hit = (ok >> 1) & 1u;
             ok &= 1u;
             if (tab_n != 0 && tid < nks) {  // comb tables loaded over the keystreams ahead
@@ -2076,6 +2103,9 @@ hipError_t launch_resident(const Batch &b, const ResArgs &a, hipStream_t s) {
 
 hipError_t launch_one(bool seal, const Batch &b, hipStream_t s) {
     if (b.n == 0 || ((uintptr_t)b.arena & 15)) return hipErrorInvalidValue;
+    // additional data past 4 bytes: a lone packet whose record and tail fit the staging area together
+    if (b.aad_len > 4 && (b.n != 1 || b.descs || !one_fits_launch(b.uniform_len, seal, b.aad_len)))
+        return hipErrorInvalidValue;
     if (!b.descs) {  // uniform: slots that hold the 16-B-rounded staging area and fit it in LDS
         const uint64_t stage = (4ull + b.uniform_len + (seal ? QGCM_OVERHEAD : 0) + 15) & ~15ull;
         if ((b.n > 1 && (b.stride < stage || (b.stride & 15))) || stage > kOneCap - 16 ||

@@ -100,6 +100,12 @@ struct qgcm_ctx {
     // pool slots stay small (the latency kernel's LDS staging limit): payloads up to ~32 KiB, which
     // covers every packet quantum sends (MTU 1433, jumbo 9000); larger calls share one big slot
     static constexpr size_t kOneSlotCap = kOneCap + 4096;
+    // a long-AAD call's staging -- record + tail (at most kOneCap - 16 under one_fits_launch) + the 16
+    // status bytes behind them -- never leaves the pool's slots; the largest fitting call as a witness
+    static_assert((kOneCap - 16u) + 16u <= kOneSlotCap, "record, tail and status bytes fit a pooled staging slot");
+    static_assert(one_fits_launch(16336, true, QGCM_MAX_AAD) && !one_fits_launch(16337, true, QGCM_MAX_AAD) &&
+                      one_record_bytes(16336, true) + one_tail_bytes(QGCM_MAX_AAD) + 16u <= kOneSlotCap,
+                  "the largest long-AAD call fits a pooled staging slot");
     OneSlot one[kOneSlots];
     OneSlot big;  // calls whose staging exceeds kOneSlotCap (released after the call past 64 MiB)
     std::atomic<uint32_t> one_rr{0};
@@ -235,9 +241,12 @@ int run_uniform(qgcm_ctx *ctx, bool seal, uint8_t *arena, uint64_t stride, uint3
 // With the latency kernel the call completes on its flag (status[1], written last by the kernel,
 // after a system-scope fence) instead of hipStreamSynchronize: the host spins on pinned memory for
 // up to 1 s, then falls back to the stream (which also reports a failed launch or a fault).
+// aad_len > 4 (the additional data as a tail behind the slot, one_fit.h): the latency kernel or nothing
+// -- the batch kernel has no long-AAD form, so the caller has checked one_kernel and the fit.
 int run_one(qgcm_ctx *ctx, bool seal, uint8_t *slot, uint64_t stride, uint32_t len, uint32_t key_idx,
             uint32_t aad_len, uint8_t *status, hipStream_t s) {
-    if (ctx->one_kernel && stride <= kOneCap - 16 && !(stride & 15) && !((uintptr_t)slot & 15)) {
+    if (ctx->one_kernel && stride + one_tail_bytes(aad_len) <= kOneCap - 16 && !(stride & 15) &&
+        !((uintptr_t)slot & 15)) {
         volatile uint8_t *done = status + 1;
         *done = 0;
         Batch b = base_batch(ctx);
@@ -261,6 +270,7 @@ int run_one(qgcm_ctx *ctx, bool seal, uint8_t *slot, uint64_t stride, uint32_t l
         std::atomic_thread_fence(std::memory_order_acquire);
         return QGCM_OK;
     }
+    if (aad_len > 4) return QGCM_E_ARG;
     const int rc = run_uniform(ctx, seal, slot, stride, 1, len, key_idx, nullptr, aad_len, status, s);
     return rc == QGCM_OK ? hip_fail(hipStreamSynchronize(s)) : rc;
 }
@@ -868,7 +878,10 @@ int qgcm_open_uniform(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t
 
 long qgcm_seal_one(qgcm_ctx *ctx, uint32_t key_idx, uint8_t *data, long length, const uint8_t *aad, uint32_t aad_len,
                    const uint8_t *nonce) {
-    if (!ctx || !data || length < 0 || length >= (long)QGCM_MAX_PAYLOAD || aad_len > 4 || (aad_len && !aad)) return -1;
+    if (!ctx || !data || length < 0 || length >= (long)QGCM_MAX_PAYLOAD || aad_len > QGCM_MAX_AAD || (aad_len && !aad))
+        return -1;
+    // additional data past the record's 4 bytes: the latency engine alone, record and tail together
+    if (aad_len > 4 && (!ctx->one_kernel || !one_fits_launch((uint64_t)length, true, aad_len))) return -1;
     if (!key_ok(ctx, key_idx)) return -1;
     if (Resident *r = get_resident(ctx)) {  // no launch per call (and no HIP call); draws the nonce if NULL
         const long rc = resident_call(r, true, key_idx, data, length, aad, aad_len, nonce);
@@ -884,29 +897,34 @@ long qgcm_seal_one(qgcm_ctx *ctx, uint32_t key_idx, uint8_t *data, long length, 
         return -1;
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-    const uint64_t stride = ((uint64_t)length + 4 + QGCM_OVERHEAD + 15) & ~15ull;
+    const uint64_t stride = one_record_bytes((uint64_t)length, true);
+    const uint64_t tail = one_tail_bytes(aad_len), sb = stride + tail;  // status and done bytes behind the tail
+    if (tail && sb + 16 > qgcm_ctx::kOneSlotCap) return -1;  // cannot happen under one_fits_launch (static_assert there)
     std::unique_lock<std::mutex> lk;
-    qgcm_ctx::OneSlot *sl = acquire_one(ctx, stride + 16, lk);
+    qgcm_ctx::OneSlot *sl = acquire_one(ctx, sb + 16, lk);
     if (!sl) return -1;
     const BigRelease rel{ctx, sl};
     uint8_t *h = sl->h;
-    memset(h, 0, stride);
-    if (aad_len) memcpy(h, aad, aad_len);
+    memset(h, 0, sb);
+    if (aad_len) memcpy(tail ? h + stride : h, aad, aad_len);
     memcpy(h + 4, data, (size_t)length);
     memcpy(h + 4 + length + 16, nb, 12);
     // Zero-copy: the kernel seals the pinned staging slot in place over PCIe (one packet: no DMA
     // setups; the copy-in / copy-out form took ~3x longer per call)
     hipStream_t s = sl->stream;
-    h[stride] = 0;
-    if (run_one(ctx, true, h, stride, (uint32_t)length, key_idx, aad_len, h + stride, s) != QGCM_OK) return -1;
-    if (h[stride] != 1) return -1;
+    h[sb] = 0;
+    if (run_one(ctx, true, h, stride, (uint32_t)length, key_idx, aad_len, h + sb, s) != QGCM_OK) return -1;
+    if (h[sb] != 1) return -1;
     memcpy(data, h + 4, (size_t)length + QGCM_OVERHEAD);
     return length + QGCM_OVERHEAD;
 }
 
 long qgcm_open_one(qgcm_ctx *ctx, uint32_t key_idx, uint8_t *data, long len, const uint8_t *aad, uint32_t aad_len) {
-    if (!ctx || (!data && len) || len < 0 || len - QGCM_OVERHEAD >= (long)QGCM_MAX_PAYLOAD || aad_len > 4 || (aad_len && !aad)) return -1;
+    if (!ctx || (!data && len) || len < 0 || len - QGCM_OVERHEAD >= (long)QGCM_MAX_PAYLOAD || aad_len > QGCM_MAX_AAD ||
+        (aad_len && !aad))
+        return -1;
     if (len < QGCM_OVERHEAD) return -1;  // crypto/aes.go:58-60: errOpen (the reference panics below 12)
+    if (aad_len > 4 && (!ctx->one_kernel || !one_fits_launch((uint64_t)len, false, aad_len))) return -1;  // as qgcm_seal_one
     if (!key_ok(ctx, key_idx)) return -1;
     if (Resident *r = get_resident(ctx)) {  // no launch per call (and no HIP call)
         const long rc = resident_call(r, false, key_idx, data, len, aad, aad_len, nullptr);
@@ -916,20 +934,22 @@ long qgcm_open_one(qgcm_ctx *ctx, uint32_t key_idx, uint8_t *data, long len, con
         }
     }
     if (hipSetDevice(ctx->device) != hipSuccess) return -1;
-    const uint64_t stride = ((uint64_t)len + 4 + 15) & ~15ull;
+    const uint64_t stride = one_record_bytes((uint64_t)len, false);
+    const uint64_t tail = one_tail_bytes(aad_len), sb = stride + tail;
+    if (tail && sb + 16 > qgcm_ctx::kOneSlotCap) return -1;  // cannot happen under one_fits_launch (static_assert there)
     std::unique_lock<std::mutex> lk;
-    qgcm_ctx::OneSlot *sl = acquire_one(ctx, stride + 16, lk);
+    qgcm_ctx::OneSlot *sl = acquire_one(ctx, sb + 16, lk);
     if (!sl) return -1;
     const BigRelease rel{ctx, sl};
     uint8_t *h = sl->h;
-    memset(h, 0, stride);
-    if (aad_len) memcpy(h, aad, aad_len);
+    memset(h, 0, sb);
+    if (aad_len) memcpy(tail ? h + stride : h, aad, aad_len);
     memcpy(h + 4, data, (size_t)len);
     hipStream_t s = sl->stream;  // zero-copy on the pinned staging slot, as qgcm_seal_one
-    h[stride] = 0;
-    if (run_one(ctx, false, h, stride, (uint32_t)len, key_idx, aad_len, h + stride, s) != QGCM_OK) return -1;
+    h[sb] = 0;
+    if (run_one(ctx, false, h, stride, (uint32_t)len, key_idx, aad_len, h + sb, s) != QGCM_OK) return -1;
     memcpy(data, h + 4, (size_t)len - QGCM_OVERHEAD);  // plaintext, or zeros on auth failure
-    return h[stride] == 1 ? len - QGCM_OVERHEAD : -1;
+    return h[sb] == 1 ? len - QGCM_OVERHEAD : -1;
 }
 
 // Host batches, pipelined: the batch is cut into ~64 MiB chunks, each with its own device slot while

@@ -66,6 +66,8 @@ std::pair<uint32_t, Error> GPUContext::AllocSlot() {
 
 // crypto/aes.go:41-52.  The nonce comes from getrandom inside qgcm_seal_one (crypto/rand); an RNG
 // failure is the reference's only Encrypt error, a too-small buffer is a Go panic: both -> error.
+// `additional` goes through at its own length (up to QGCM_MAX_AAD; qgcm.h has the one size rule for
+// more than 4 bytes, beyond which the call fails with data untouched).
 std::pair<int, Error> AES::Encrypt(common::Slice data, int length, common::Slice additional) const {
     if (length < 0 || (size_t)length + Overhead + NonceSize > data.cap)
         return {-1, Error{"crypto: buffer too small for the tag and nonce"}};
@@ -75,7 +77,8 @@ std::pair<int, Error> AES::Encrypt(common::Slice data, int length, common::Slice
     return {(int)n, Error{}};
 }
 
-// crypto/aes.go:57-62: returns DecryptedSize(data) together with the error, as Go does.
+// crypto/aes.go:57-62: returns DecryptedSize(data) together with the error, as Go does (additional
+// data past qgcm.h's size rule fails like a tag mismatch, data untouched).
 std::pair<int, Error> AES::Decrypt(common::Slice data, common::Slice additional) const {
     const long n = qgcm_open_one(ctx_, slot_, data.data, (long)data.len,
                                  additional.len ? additional.data : nullptr, (uint32_t)additional.len);

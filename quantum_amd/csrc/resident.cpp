@@ -415,8 +415,10 @@ struct WaitState {
 
 long resident_call(Resident *r, bool seal, uint32_t key, uint8_t *data, long len, const uint8_t *aad,
                    uint32_t aad_len, const uint8_t *nonce) {
-    const uint64_t stage = (4ull + (uint64_t)len + (seal ? QGCM_OVERHEAD : 0) + 15) & ~15ull;
-    if (!r || r->broken || stage > kResSlotBytes || stage > kOneCap - 16) return kResNotServed;
+    // the record and, for additional data past its 4 bytes, the tail behind it (one_fit.h) fit a slot
+    // and the engine's staging area; the worker's own test is the same one
+    const uint64_t stage = one_record_bytes((uint64_t)len, seal), tail = one_tail_bytes(aad_len);
+    if (!r || r->broken || !one_fits_resident((uint64_t)len, seal, aad_len, false)) return kResNotServed;
     // a free slot of this thread's home worker, else of the next workers in turn
     static std::atomic<uint32_t> next_thread{0};
     thread_local const uint32_t t_index = next_thread.fetch_add(1, std::memory_order_relaxed);
@@ -458,7 +460,8 @@ long resident_call(Resident *r, bool seal, uint32_t key, uint8_t *data, long len
             r->busy[s].store(0, std::memory_order_release);
             return -1;
         }
-        if (r->ahead && stage + 16 <= kResSlotBytes && random_nonce(nx)) {
+        // (not where the tail would reach the announced nonce's row: that call does not announce)
+        if (r->ahead && one_fits_resident((uint64_t)len, seal, aad_len, true) && random_nonce(nx)) {
             r->next_gen[s] = fg;
             announce = true;
         }
@@ -468,17 +471,21 @@ long resident_call(Resident *r, bool seal, uint32_t key, uint8_t *data, long len
     // sequence; sfence orders the first stores before it and pushes it out
     uint8_t *slot = r->in + (size_t)s * kResSlotBytes;
     uint32_t hdr = 0;
-    if (aad_len) memcpy(&hdr, aad, aad_len);
+    if (aad_len && !tail) memcpy(&hdr, aad, aad_len);
     memcpy(slot, &hdr, 4);
     memcpy(slot + 4, data, (size_t)len);
     if (seal) memcpy(slot + 4 + len + 16, nb, 12);
+    if (tail) {  // the slot holds an earlier request's bytes: the tail's padding is written as zeros
+        memcpy(slot + stage, aad, aad_len);
+        memset(slot + stage + aad_len, 0, (size_t)(tail - aad_len));
+    }
     if (announce) memcpy(slot + kResSlotBytes - 16, &r->next_nonce[12ull * s], 12);
     const uint32_t q0 = r->seqh[s];
     uint32_t q = (q0 + 1) & 0x7fffffffu;
     if (q == 0) q = 1;
     r->seqh[s] = q;
     _mm_store_si128(reinterpret_cast<__m128i *>(&r->req[s]),
-                    _mm_set_epi32((int)key, (int)len, (int)((seal ? 1u : 0u) | aad_len << 1 | (announce ? 1u : 0u) << 8),
+                    _mm_set_epi32((int)key, (int)len, (int)((seal ? 1u : 0u) | (announce ? 1u : 0u) << 8 | aad_len << 16),
                                   (int)q0));
     _mm_sfence();  // the slot bytes and the record's fields before the sequence
     __atomic_store_n(reinterpret_cast<uint32_t *>(&r->req[s]), q, __ATOMIC_RELAXED);
