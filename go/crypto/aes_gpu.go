@@ -44,6 +44,9 @@ package crypto
 #cgo LDFLAGS: -L${SRCDIR}/../vendor/qgcm/lib -lqgcm -Wl,-rpath,${SRCDIR}/../vendor/qgcm/lib
 #include <stdlib.h>
 #include <qgcm.h>
+
+// QGCM_NONCES_GENERATE is a cast expression, which cgo cannot turn into a Go constant
+static const uint8_t *qgcm_go_nonces_generate(void) { return QGCM_NONCES_GENERATE; }
 */
 import "C"
 
@@ -427,6 +430,29 @@ func (gg *GPUGroup) SealBatch(arena *Arena, descs []Desc, status []byte) (int, e
 	}
 	rc := C.qgcm_group_seal_host(gg.grp, (*C.uint8_t)(arena.p), (*C.qgcm_desc)(unsafe.Pointer(&descs[0])),
 		C.uint32_t(n), (*C.uint8_t)(gg.nonces), 4, bytePtr(status))
+	if rc < 0 {
+		return 0, fmt.Errorf("qgcm: group seal: %s", C.GoString(C.qgcm_strerror(rc)))
+	}
+	return int(rc), nil
+}
+
+// SealBatchGenerated is SealBatch with the nonces drawn on the GPUs: each member writes its packets'
+// nonces into their slots from its context's AES-256-CTR generator (keyed from getrandom(2), reseeded
+// every QGCM_NONCE_RESEED nonces; qgcm.h QGCM_NONCES_GENERATE) and seals with them.  No nonce buffer, no
+// getrandom call per batch and no copy of nonces to the device: the form for large batches (INTEGRATION.md
+// s2 says from which size it pays).  Slots, status and the return value are as for SealBatch.
+func (gg *GPUGroup) SealBatchGenerated(arena *Arena, descs []Desc, status []byte) (int, error) {
+	if err := checkBatch(arena, descs, status, true); err != nil {
+		return 0, err
+	}
+	n := len(descs)
+	if n == 0 {
+		return 0, nil
+	}
+	gg.bmu.Lock()
+	defer gg.bmu.Unlock()
+	rc := C.qgcm_group_seal_host(gg.grp, (*C.uint8_t)(arena.p), (*C.qgcm_desc)(unsafe.Pointer(&descs[0])),
+		C.uint32_t(n), C.qgcm_go_nonces_generate(), 4, bytePtr(status))
 	if rc < 0 {
 		return 0, fmt.Errorf("qgcm: group seal: %s", C.GoString(C.qgcm_strerror(rc)))
 	}

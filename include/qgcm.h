@@ -106,7 +106,8 @@ int qgcm_x25519(uint8_t secret[32], const uint8_t priv[32], const uint8_t peer_p
 /* ---- device batches (the throughput path) ---- */
 /* Seal n packets in place.  nonces: device array of n*12 bytes (nonce i for packet i, written
  * into the slot like crypto/aes.go:50), or NULL to use the nonce already present at
- * [4+L+16, 4+L+28) of each slot.  aad_len: 0 (nil additional) or 4 (the Payload IP header).
+ * [4+L+16, 4+L+28) of each slot, or QGCM_NONCES_GENERATE to have the library draw them on the GPU (see
+ * "nonce source" below; the same three forms in every batch seal).  aad_len: 0 (nil additional) or 4 (the Payload IP header).
  * status (device, n bytes, may be NULL): 1 = sealed, 0 = rejected (key index out of range or never set,
  * payload of QGCM_MAX_PAYLOAD or more; the slot is untouched). */
 int qgcm_seal_batch(qgcm_ctx *ctx, uint8_t *d_arena, const qgcm_desc *d_descs, uint32_t n,
@@ -210,7 +211,8 @@ int qgcm_group_clear_keys(qgcm_group *g, uint32_t first_idx, uint32_t count);
  * capacity 4 + L + 28; open: len = L + 28), any key mix.  Packets are split by owner; one host thread and
  * one stream set per member gathers its packets into pinned staging, copies them to its device, runs the
  * descriptor batch, copies back and writes the results into the same slots (input order kept).
- * h_nonces: n * 12 B (seal; NULL = nonce already in the slot).  h_status[i] (may be NULL): 1 ok, 0 failed
+ * h_nonces: n * 12 B (seal; NULL = nonce already in the slot; QGCM_NONCES_GENERATE = each member draws its
+ * packets' nonces on its GPU).  h_status[i] (may be NULL): 1 ok, 0 failed
  * (as qgcm_seal_batch / qgcm_open_batch).  Returns the number of failed packets or a negative error.
  * One call at a time per group (calls are serialized).  When h_arena (and h_nonces) is pinned host memory
  * (qgcm_host_alloc, hipHostMalloc, hipHostRegister) holding every record, the members' GPUs gather and
@@ -252,6 +254,32 @@ void qgcm_host_free(void *p);
 /* ---- nonce source for production seals (crypto/aes.go:42-47 draws per packet) ---- */
 /* Fills n*12 bytes of host memory from getrandom(2). */
 int qgcm_random_nonces(uint8_t *h_out, uint32_t n);
+/* Nonces generated on the GPU.  Each context owns an AES-256-CTR generator (SP 800-38A counter mode): a
+ * key K (32 B) and a 128-bit counter V, both drawn from getrandom(2) on first use.  Nonce number j of the
+ * stream is the first 12 bytes of AES-256_K(BE128(V0 + j)), the counter a big-endian 128-bit integer.  A
+ * call that needs n nonces reserves [V, V + n) and carries its own copy of the round keys to the device,
+ * so calls on different streams or threads never share a position and never see each other's reseed.
+ * Reseed rule: before reserving, when at least one nonce was drawn since the last (re)seed and that count
+ * plus n would exceed the reseed interval (QGCM_NONCE_RESEED at qgcm_create, default 2^32), K and V are
+ * drawn anew from getrandom(2); one call always uses one key.  GCM needs nonces that never repeat under a
+ * key, not secret ones: they travel in the clear behind every packet.
+ *
+ * QGCM_NONCES_GENERATE as the nonce argument of qgcm_seal_uniform, qgcm_seal_batch, qgcm_seal_host or
+ * qgcm_group_seal_host: the library writes nonce j of the call's reservation into packet j's nonce field
+ * ([4+L+16, 4+L+28) of the slot) with a kernel on the call's stream, then seals with the nonce in the
+ * slot.  No nonce array, no host round trip; pinned arenas sealed in place get their nonces over PCIe from
+ * the same kernel.  A packet the seal rejects (status 0) gets no nonce -- its slot stays untouched -- but
+ * keeps its stream position.  A call refused with QGCM_E_ARG or QGCM_E_KEY, or with n = 0, draws nothing.
+ * Group calls draw from each member's own context.  qgcm_compress_seal_host does not take it (QGCM_E_ARG).
+ * QGCM_E_NOMEM from such a call: getrandom(2) failed, nothing was written. */
+#define QGCM_NONCES_GENERATE ((const uint8_t *)(uintptr_t)1)
+/* Writes the next n nonces of ctx's generator to d_out (device memory, n*12 bytes, 4-B aligned).
+ * Asynchronous on stream. */
+int qgcm_nonce_fill(qgcm_ctx *ctx, uint8_t *d_out, uint32_t n, void *stream);
+/* Sets the generator's key and counter (BE128) and restarts the reseed count: the hook for known-answer
+ * tests and reproducible runs.  Two contexts seeded alike produce the same nonces -- never do that with a
+ * key that seals traffic.  key NULL (counter ignored): reseed from getrandom(2) now. */
+int qgcm_nonce_seed(qgcm_ctx *ctx, const uint8_t key[32], const uint8_t counter[16]);
 
 /* ---- snappy block format: the compression plugin (plugin/compression.go) ---- */
 /* Host codec (C++; golang/snappy is not in the reference).  Encode restates golang/snappy's block

@@ -22,7 +22,7 @@ EXPORTS = (
     "qgcm_x25519_base", "qgcm_x25519",
     "qgcm_seal_batch", "qgcm_open_batch", "qgcm_seal_uniform", "qgcm_open_uniform",
     "qgcm_seal_one", "qgcm_open_one", "qgcm_seal_host", "qgcm_open_host",
-    "qgcm_random_nonces", "qgcm_fill_uniform", "qgcm_host_alloc", "qgcm_host_free",
+    "qgcm_random_nonces", "qgcm_nonce_fill", "qgcm_nonce_seed", "qgcm_fill_uniform", "qgcm_host_alloc", "qgcm_host_free",
     "qgcm_stream_copy",
     "qgcm_snappy_max_compressed_length", "qgcm_snappy_compress", "qgcm_snappy_uncompressed_length",
     "qgcm_snappy_uncompress", "qgcm_snappy_compress_slots", "qgcm_snappy_uncompress_slots",
@@ -45,6 +45,9 @@ QGCM_E_NOMEM = -5
 OVERHEAD = 28
 QGCM_MAX_AAD = 16384  # longest additional data of a per-packet call (qgcm_seal_one / qgcm_open_one)
 ERRLEN = 120
+# QGCM_NONCES_GENERATE: as the nonce argument of a batch seal, "draw the nonces on the GPU from the
+# context's AES-256-CTR generator and write them into the slots" (include/qgcm.h)
+NONCES_GENERATE = 1
 
 
 class QgcmError(RuntimeError):
@@ -90,6 +93,9 @@ def _bind(L: C.CDLL) -> None:
     L.qgcm_seal_host.argtypes = [vp, vp, u64, u32, u32, u32, vp, u32, vp]
     L.qgcm_open_host.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp]
     L.qgcm_random_nonces.argtypes = [vp, u32]
+    if hasattr(L, "qgcm_nonce_fill"):  # (older builds loaded by the A/B tools lack the nonce generator)
+        L.qgcm_nonce_fill.argtypes = [vp, vp, u32, vp]
+        L.qgcm_nonce_seed.argtypes = [vp, u8p, u8p]
     L.qgcm_host_alloc.argtypes = [C.c_size_t]
     L.qgcm_host_alloc.restype = vp
     L.qgcm_host_free.argtypes = [vp]

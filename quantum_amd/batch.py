@@ -26,15 +26,45 @@ def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else int(t.data_ptr())
 
 
+class _Generate:
+    """The `nonces` argument that stands for QGCM_NONCES_GENERATE (see GENERATE)."""
+
+    def __repr__(self) -> str:  # pragma: no cover - message only
+        return "GENERATE"
+
+
+# As `nonces` of seal_uniform / seal_batch (and as the nonce address of the host and group seals, where
+# it is _lib.NONCES_GENERATE): the library draws the nonces on the GPU from the context's AES-256-CTR
+# generator and writes them into the slots' nonce fields, on the call's stream (include/qgcm.h).
+GENERATE = _Generate()
+
+
+def _nonce_ptr(nonces) -> int | None:
+    return _lib.NONCES_GENERATE if nonces is GENERATE else _ptr(nonces)
+
+
+def nonce_fill(ctx: Context, out: torch.Tensor, n: int, stream: torch.cuda.Stream | None = None) -> None:
+    """The next n nonces of ctx's generator into `out` (device uint8, n * 12 bytes, 4-B aligned)."""
+    _lib.check(_lib.lib().qgcm_nonce_fill(ctx.handle, _ptr(out), n, _stream_handle(stream)), "qgcm_nonce_fill")
+
+
+def nonce_seed(ctx: Context, key: bytes | None = None, counter: bytes | None = None) -> None:
+    """Sets the generator's key (32 B) and counter (16 B, big-endian) -- known answers and reproducible
+    runs only: two contexts seeded alike repeat nonces.  key None: reseed from getrandom now."""
+    if key is not None and (len(key) != 32 or counter is None or len(counter) != 16):
+        raise ValueError("nonce_seed takes a 32-byte key and a 16-byte counter")
+    _lib.check(_lib.lib().qgcm_nonce_seed(ctx.handle, key, counter if key is not None else None), "qgcm_nonce_seed")
+
+
 def slot_stride(max_len: int, align: int = 16) -> int:
     """Smallest multiple of `align` holding [aad 4][payload][tag 16][nonce 12]."""
     return (4 + max_len + _lib.OVERHEAD + align - 1) // align * align
 
 
 def seal_uniform(ctx: Context, arena: torch.Tensor, stride: int, n: int, length: int, key_idx: int,
-                 nonces: torch.Tensor | None = None, aad_len: int = AAD_LEN, status: torch.Tensor | None = None,
-                 stream: torch.cuda.Stream | None = None) -> None:
-    _lib.check(_lib.lib().qgcm_seal_uniform(ctx.handle, _ptr(arena), stride, n, length, key_idx, _ptr(nonces),
+                 nonces: torch.Tensor | _Generate | None = None, aad_len: int = AAD_LEN,
+                 status: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> None:
+    _lib.check(_lib.lib().qgcm_seal_uniform(ctx.handle, _ptr(arena), stride, n, length, key_idx, _nonce_ptr(nonces),
                                             aad_len, _ptr(status), _stream_handle(stream)), "qgcm_seal_uniform")
 
 
@@ -58,10 +88,10 @@ def make_descs(offsets, lengths, keys, device) -> torch.Tensor:
     return words.contiguous().view(torch.uint8).reshape(-1).to(device)
 
 
-def seal_batch(ctx: Context, arena: torch.Tensor, descs: torch.Tensor, n: int, nonces: torch.Tensor | None = None,
-               aad_len: int = AAD_LEN, status: torch.Tensor | None = None,
-               stream: torch.cuda.Stream | None = None) -> None:
-    _lib.check(_lib.lib().qgcm_seal_batch(ctx.handle, _ptr(arena), _ptr(descs), n, _ptr(nonces), aad_len,
+def seal_batch(ctx: Context, arena: torch.Tensor, descs: torch.Tensor, n: int,
+               nonces: torch.Tensor | _Generate | None = None, aad_len: int = AAD_LEN,
+               status: torch.Tensor | None = None, stream: torch.cuda.Stream | None = None) -> None:
+    _lib.check(_lib.lib().qgcm_seal_batch(ctx.handle, _ptr(arena), _ptr(descs), n, _nonce_ptr(nonces), aad_len,
                                           _ptr(status), _stream_handle(stream)), "qgcm_seal_batch")
 
 
@@ -100,6 +130,15 @@ def snappy_uncompress(ctx: Context, arena: torch.Tensor, stride: int, n: int, le
 def host_ptr(buf: bytearray) -> tuple[int, object]:
     arr = (C.c_uint8 * len(buf)).from_buffer(buf)
     return C.addressof(arr), arr
+
+
+def seal_host(ctx: Context, arena_ptr: int, stride: int, n: int, length: int, key_idx: int, nonces=None,
+              aad_len: int = AAD_LEN, status_ptr: int | None = None) -> int:
+    """qgcm_seal_host on host slots at arena_ptr; `nonces`: a host address (n * 12 B), None (the nonce is in
+    the slot) or GENERATE.  Returns the number of packets that failed."""
+    np_ = _lib.NONCES_GENERATE if nonces is GENERATE else nonces
+    return _lib.check(_lib.lib().qgcm_seal_host(ctx.handle, arena_ptr, stride, n, length, key_idx, np_, aad_len,
+                                                status_ptr), "qgcm_seal_host")
 
 
 def compress_seal_host(ctx: Context, arena_ptr: int, stride: int, n: int, lens, key_idx: int, nonces_ptr: int | None,

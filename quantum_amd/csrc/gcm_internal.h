@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/qgcm.h"
+#include "nonce_rng.h"
 #include "one_fit.h"
 
 namespace qgcm {
@@ -249,5 +250,27 @@ hipError_t launch_key_setup(const uint8_t *d_keys, uint32_t first, uint32_t coun
                             uint4 *gh_table, const uint8_t *d_sbox, hipStream_t s);
 hipError_t launch_fill_uniform(uint8_t *arena, uint64_t stride, uint32_t n, uint32_t len, uint32_t aad_word,
                                uint64_t seed_payload, uint8_t *nonces, uint64_t seed_nonce, hipStream_t s);
+
+// Nonce generator (nonce_rng.h): nonce j = the first 12 bytes of AES-256_K(BE128(V + j)), one lane per
+// nonce.  The round keys travel by value in the kernel arguments, so a reseed on the host never changes
+// what a launch still in flight on another stream computes.
+struct NonceArgs {
+    NonceKeys keys;             // 480 B
+    uint32_t v0, v1, v2, v3;    // counter of nonce 0, v0 least significant
+    uint8_t *out;               // array: n * 12 B, 4-B aligned; slots: the arena
+    const qgcm_desc *descs;     // descriptor slots: packet j is descs[j]
+    const uint8_t *key_valid;   // descriptor slots: [max_keys]
+    const uint32_t *te;         // [512] Te0 then Te1
+    uint64_t stride;            // uniform slots: slot j at j * stride
+    uint32_t len;               // uniform slots: payload length L (the field is at [4+L+16, 4+L+28))
+    uint32_t n;
+    uint32_t max_keys;
+    uint32_t one;               // descriptor slots: the seal is gcm_one_kernel's (run_descs_one), which also
+                                // rejects records off a 16-B boundary or past its staging area
+};
+enum NonceDest { kNonceArray = 0, kNonceUniform = 1, kNonceDescs = 2 };
+// A packet the seal will reject (key index out of range or unset, payload of QGCM_MAX_PAYLOAD or more)
+// gets no nonce -- its slot stays untouched -- but keeps its stream position.
+hipError_t launch_nonce_fill(NonceDest dest, const NonceArgs &a, int num_cus, hipStream_t s);
 
 }  // namespace qgcm

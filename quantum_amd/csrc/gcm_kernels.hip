@@ -2139,6 +2139,8 @@ static int variant_slot(int v) {
     return v == kVariantUniform ? 0 : v == kVariantDescWave ? 1 : v == kVariantDescQuad ? 2 : -1;
 }
 
+static const void *nonce_kernel_of(NonceDest dest);  // the nonce generator's kernels, at the end of the file
+
 hipError_t init_kernels() {
     g_variants[0] = Variant{reinterpret_cast<const void *>(&gcm_quad_kernel<true, false>),
                                           reinterpret_cast<const void *>(&gcm_quad_kernel<false, false>),
@@ -2172,6 +2174,15 @@ hipError_t init_kernels() {
         if (a.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
         e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 k == reinterpret_cast<const void *>(&gcm_resident_kernel) ? kResLds : kOneLds);
+        if (e != hipSuccess) return e;
+    }
+    for (NonceDest d : {kNonceArray, kNonceUniform, kNonceDescs}) {  // T-tables at LDS 0, as above
+        const void *k = nonce_kernel_of(d);
+        hipFuncAttributes a;
+        hipError_t e = hipFuncGetAttributes(&a, k);
+        if (e != hipSuccess) return e;
+        if (a.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kTeBytes);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -2513,6 +2524,86 @@ hipError_t launch_fill_uniform(uint8_t *arena, uint64_t stride, uint32_t n, uint
     hipLaunchKernelGGL(fill_uniform_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(bs), 0, s, arena, stride, n,
                        len, aad_word, seed_payload, nonces, seed_nonce);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// Nonce generator (nonce_rng.h): nonce j = the first 12 bytes of
+// AES-256_K(BE128(V + j)), one lane per nonce, 14 table rounds on the replicated T-tables in LDS (64 KiB,
+// so two workgroups fit a CU).  The round keys are kernel arguments (uniform, constant indices after
+// unrolling: scalar loads from the argument segment).  Persistent grid-stride grid.
+
+// 12 bytes at p (any alignment): aligned dwords inside, single bytes at the edges, nothing outside
+__device__ __forceinline__ void store_nonce(uint8_t *p, uint32_t n0, uint32_t n1, uint32_t n2) {
+    const uint32_t a = (uint32_t)(uintptr_t)p & 3u;
+    if (a == 0) {
+        uint32_t *q = reinterpret_cast<uint32_t *>(p);
+        q[0] = n0;
+        q[1] = n1;
+        q[2] = n2;
+        return;
+    }
+    const uint32_t sh = 8u * a, rs = 32u - sh;  // sh, rs in {8, 16, 24}
+    uint32_t *q = reinterpret_cast<uint32_t *>(p - a);
+    store_bytes(p, n0, 4u - a);
+    q[1] = (n0 >> rs) | (n1 << sh);
+    q[2] = (n1 >> rs) | (n2 << sh);
+    store_bytes(p + 12u - a, n2 >> rs, a);
+}
+
+template <int kDest>
+__global__ void __launch_bounds__(kOneThreads) nonce_kernel(NonceArgs a) {
+    const uint32_t tid = threadIdx.x, lb = (tid & 31u) << 2;
+    one_fill_te(a.te, tid);
+    __syncthreads();
+    const Keys kk = {a.keys.rk, a.keys.rr};
+    const uint32_t step = gridDim.x * kOneThreads;  // n <= 2^31 and step <= 2^20: j + step stays below 2^32
+    for (uint32_t j = blockIdx.x * kOneThreads + tid; j < a.n; j += step) {
+        uint8_t *dst;
+        if constexpr (kDest == kNonceArray) {
+            dst = a.out + 12ull * j;
+        } else if constexpr (kDest == kNonceUniform) {
+            dst = a.out + (uint64_t)j * a.stride + 4ull + a.len + 16ull;
+        } else {
+            // as the seal kernels reject (worklist.hip, gcm_one_kernel): no nonce, the slot stays untouched
+            const qgcm_desc d = a.descs[j];
+            bool ok = d.key_idx < a.max_keys && d.len < QGCM_MAX_PAYLOAD;
+            ok = ok && a.key_valid[d.key_idx] != 0;
+            if (a.one) ok = ok && !(d.offset & 15u) && ((4ull + d.len + QGCM_OVERHEAD + 15ull) & ~15ull) <= kOneCap - 16u;
+            if (!ok) continue;
+            dst = a.out + d.offset + 4ull + d.len + 16ull;
+        }
+        // BE128(V + j): the counter's least significant limb is the block's last word
+        const uint32_t c0 = a.v0 + j;
+        uint32_t cy = c0 < j ? 1u : 0u;
+        const uint32_t c1 = a.v1 + cy;
+        cy = c1 < cy ? 1u : 0u;
+        const uint32_t c2 = a.v2 + cy;
+        cy = c2 < cy ? 1u : 0u;
+        const uint32_t c3 = a.v3 + cy;
+        uint32_t s0 = bswap(c3) ^ kk.rk[0], s1 = bswap(c2) ^ kk.rk[1], s2 = bswap(c1) ^ kk.rk[2],
+                 s3 = bswap(c0) ^ kk.rk[3];
+#pragma unroll
+        for (int r = 1; r < 14; ++r) round_full(s0, s1, s2, s3, kk, r, lb);
+        round_last(s0, s1, s2, s3, kk, lb);
+        store_nonce(dst, s0, s1, s2);
+    }
+}
+
+static const void *nonce_kernel_of(NonceDest dest) {
+    return dest == kNonceArray     ? reinterpret_cast<const void *>(&nonce_kernel<kNonceArray>)
+           : dest == kNonceUniform ? reinterpret_cast<const void *>(&nonce_kernel<kNonceUniform>)
+                                   : reinterpret_cast<const void *>(&nonce_kernel<kNonceDescs>);
+}
+
+hipError_t launch_nonce_fill(NonceDest dest, const NonceArgs &a, int num_cus, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    if (!a.out || !a.te || a.n > QGCM_MAX_BATCH || (dest == kNonceDescs && (!a.descs || !a.key_valid)))
+        return hipErrorInvalidValue;
+    // at most two workgroups per CU (64 KiB of LDS each), fewer when n is small
+    const uint32_t want = (uint32_t)(((uint64_t)a.n + kOneThreads - 1) / kOneThreads);
+    const uint32_t cap = 2u * (uint32_t)std::max(1, num_cus);
+    void *args[] = {const_cast<NonceArgs *>(&a)};
+    return hipLaunchKernel(nonce_kernel_of(dest), dim3(want < cap ? want : cap), dim3(kOneThreads), args, kTeBytes, s);
 }
 
 }  // namespace qgcm

@@ -197,6 +197,10 @@ inline void slice(size_t n, int i, int k, size_t &lo, size_t &hi) {
 
 using qgcm::gpu_local_cpus;
 
+// the nonce argument of a member's device batch: the caller's staged array (or NULL), or, for a call made
+// with QGCM_NONCES_GENERATE, that marker -- the member's context then writes its own nonces into the slots
+inline const uint8_t *dev_nonces(bool gen, const uint8_t *staged) { return gen ? QGCM_NONCES_GENERATE : staged; }
+
 inline uint64_t rec_bytes(bool seal, uint32_t len) {  // AAD word + packet (+ tag || nonce), 16-B aligned
     return (4ull + len + (seal ? QGCM_OVERHEAD : 0) + 15) & ~15ull;
 }
@@ -266,7 +270,7 @@ int land(Stage &s, CopyPool &pool, bool seal, uint8_t *h_arena, const qgcm_desc 
 }
 
 int run_member(Member &mb, bool seal, uint8_t *h_arena, const qgcm_desc *descs, const uint32_t *idx, size_t m,
-               const uint8_t *h_nonces, uint32_t aad_len, uint8_t *h_status, int *bad_out) {
+               const uint8_t *h_nonces, bool gen, uint32_t aad_len, uint8_t *h_status, int *bad_out) {
     int bad = 0, rc = QGCM_OK;
     // a fresh thread per call: pin it before it allocates or touches staging (first touch = local pages)
     if (mb.ncpus > 0) pthread_setaffinity_np(pthread_self(), sizeof(mb.cpus), &mb.cpus);
@@ -322,8 +326,8 @@ int run_member(Member &mb, bool seal, uint8_t *h_arena, const qgcm_desc *descs, 
             break;
         }
         const qgcm_desc *dd = reinterpret_cast<const qgcm_desc *>(s.d + off_desc);
-        rc = seal ? qgcm_seal_batch(mb.ctx, s.d, dd, (uint32_t)cn, h_nonces ? s.d + off_non : nullptr, aad_len,
-                                    s.d + off_st, s.s)
+        rc = seal ? qgcm_seal_batch(mb.ctx, s.d, dd, (uint32_t)cn, dev_nonces(gen, h_nonces ? s.d + off_non : nullptr),
+                                    aad_len, s.d + off_st, s.s)
                   : qgcm_open_batch(mb.ctx, s.d, dd, (uint32_t)cn, aad_len, s.d + off_st, s.s);
         if (rc != QGCM_OK) break;
         if (hipMemcpyAsync(s.h, s.d, bytes, hipMemcpyDeviceToHost, s.s) != hipSuccess ||
@@ -357,7 +361,7 @@ using qgcm::pinned_view;
 // Zero-copy form of run_member: the member's GPU gathers its records from the pinned arena itself.
 // v_arena / v_nonces: the arena's and nonces' device views resolved on this member's device.
 int run_member_zc(Member &mb, bool seal, uint64_t v_arena, const qgcm_desc *descs, const uint32_t *idx, size_t m,
-                  uint64_t v_nonces, uint32_t aad_len, uint8_t *h_status, int *bad_out, uint64_t chunk) {
+                  uint64_t v_nonces, bool gen, uint32_t aad_len, uint8_t *h_status, int *bad_out, uint64_t chunk) {
     ZC &z = mb.zc;
     for (Stage &s : mb.st)
         if (!s.s && hipStreamCreateWithFlags(&s.s, hipStreamNonBlocking) != hipSuccess) return QGCM_E_HIP;
@@ -432,8 +436,8 @@ int run_member_zc(Member &mb, bool seal, uint64_t v_arena, const qgcm_desc *desc
             rc = QGCM_E_HIP;
             break;
         }
-        rc = seal ? qgcm_seal_batch(mb.ctx, stage, z.d_descs + a, (uint32_t)cn, with_nonces ? stage + non_off : nullptr,
-                                    aad_len, z.d_status + a, s)
+        rc = seal ? qgcm_seal_batch(mb.ctx, stage, z.d_descs + a, (uint32_t)cn,
+                                    dev_nonces(gen, with_nonces ? stage + non_off : nullptr), aad_len, z.d_status + a, s)
                   : qgcm_open_batch(mb.ctx, stage, z.d_descs + a, (uint32_t)cn, aad_len, z.d_status + a, s);
         if (rc != QGCM_OK) break;
         // scatter: a failed seal leaves the slot untouched; open writes plaintext or zeros
@@ -580,8 +584,8 @@ int dma_ready(DmaState &z, uint64_t stage, uint64_t side, size_t slots, size_t m
 // and statuses stay in pinned host memory as well.  Returns 1 when it ran (rc in *rc), 0 when the
 // batch does not qualify (nothing done).
 int run_member_direct(Member &mb, bool allowed, bool seal, uint8_t *h_arena, const qgcm_desc *descs,
-                      const uint32_t *idx, size_t m, const uint8_t *h_nonces, uint32_t aad_len, uint8_t *h_status,
-                      int *bad_out, int *rc) {
+                      const uint32_t *idx, size_t m, const uint8_t *h_nonces, bool gen, uint32_t aad_len,
+                      uint8_t *h_status, int *bad_out, int *rc) {
     if (!allowed || !m || m > qgcm::direct_max(mb.ctx)) return 0;
     uint64_t ext = 0;
     for (size_t j = 0; j < m; ++j) {
@@ -612,8 +616,8 @@ int run_member_direct(Member &mb, bool allowed, bool seal, uint8_t *h_arena, con
     std::lock_guard<std::mutex> io(qgcm::ctx_io_mu(mb.ctx));
     hipStream_t s = qgcm::ctx_pipe(mb.ctx, 0);
     *rc = qgcm::run_descs_one(mb.ctx, seal, reinterpret_cast<uint8_t *>(va), reinterpret_cast<const qgcm_desc *>(vs),
-                              (uint32_t)m, non ? reinterpret_cast<const uint8_t *>(vs + off_non) : nullptr, aad_len,
-                              reinterpret_cast<uint8_t *>(vst), s);
+                              (uint32_t)m, dev_nonces(gen, non ? reinterpret_cast<const uint8_t *>(vs + off_non) : nullptr),
+                              aad_len, reinterpret_cast<uint8_t *>(vst), s);
     if (hipStreamSynchronize(s) != hipSuccess && *rc == QGCM_OK) *rc = QGCM_E_HIP;
     int bad = 0;
     if (*rc == QGCM_OK)
@@ -627,11 +631,11 @@ int run_member_direct(Member &mb, bool allowed, bool seal, uint8_t *h_arena, con
 }
 
 int run_member_dma(const qgcm_group *g, Member &mb, bool direct_ok, bool seal, uint8_t *h_arena,
-                   const qgcm_desc *descs, const uint32_t *idx, const DmaPlan &pl, const uint8_t *h_nonces,
+                   const qgcm_desc *descs, const uint32_t *idx, const DmaPlan &pl, const uint8_t *h_nonces, bool gen,
                    uint32_t aad_len, uint8_t *h_status, int *bad_out) {
     {
         int rc = QGCM_OK;
-        if (run_member_direct(mb, direct_ok, seal, h_arena, descs, idx, pl.at.size(), h_nonces, aad_len, h_status,
+        if (run_member_direct(mb, direct_ok, seal, h_arena, descs, idx, pl.at.size(), h_nonces, gen, aad_len, h_status,
                               bad_out, &rc))
             return rc;
     }
@@ -706,11 +710,13 @@ int run_member_dma(const qgcm_group *g, Member &mb, bool direct_ok, bool seal, u
         if (!tl.empty()) hipEventRecord(tl[3 * c], s_in);
         const qgcm_desc *dd = reinterpret_cast<const qgcm_desc *>(ds + dside);
         if (one_ok)
-            rc = qgcm::run_descs_one(mb.ctx, seal, ds, dd, (uint32_t)cn, non ? ds + dside + off_non : nullptr, aad_len,
-                                     z.d_stat + ch.j0, s_k);
+            rc = qgcm::run_descs_one(mb.ctx, seal, ds, dd, (uint32_t)cn,
+                                     dev_nonces(gen, non ? ds + dside + off_non : nullptr), aad_len, z.d_stat + ch.j0,
+                                     s_k);
         else
-            rc = seal ? qgcm_seal_batch(mb.ctx, ds, dd, (uint32_t)cn, non ? ds + dside + off_non : nullptr, aad_len,
-                                        z.d_stat + ch.j0, s_k)
+            rc = seal ? qgcm_seal_batch(mb.ctx, ds, dd, (uint32_t)cn,
+                                        dev_nonces(gen, non ? ds + dside + off_non : nullptr), aad_len, z.d_stat + ch.j0,
+                                        s_k)
                       : qgcm_open_batch(mb.ctx, ds, dd, (uint32_t)cn, aad_len, z.d_stat + ch.j0, s_k);
         if (rc != QGCM_OK) break;
         if (!tl.empty()) hipEventRecord(tl[3 * c + 1], s_k);
@@ -759,6 +765,11 @@ int run_group(qgcm_group *g, bool seal, uint8_t *h_arena, const qgcm_desc *descs
               const uint8_t *h_nonces, uint32_t aad_len, uint8_t *h_status) {
     if (!g || (n && (!h_arena || !descs)) || aad_len > 4 || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
     if (n == 0) return 0;
+    // QGCM_NONCES_GENERATE is a marker, not an array: from here on h_nonces is NULL for such a call (no
+    // pinned view, alignment check, gather or copy of nonces anywhere below) and `gen` tells each member
+    // to hand the marker to its own context's device batch, which draws from that context's generator
+    const bool gen = seal && h_nonces == QGCM_NONCES_GENERATE;
+    if (gen) h_nonces = nullptr;
     std::lock_guard<std::mutex> lk(g->call_mu);
     const int G = (int)g->m.size();
     std::vector<std::vector<uint32_t>> part(G);
@@ -829,14 +840,14 @@ int run_group(qgcm_group *g, bool seal, uint8_t *h_arena, const qgcm_desc *descs
                     mb.last_path = 2;
                     used_zc[k] = 0;
                     rc[k] = run_member_dma(g, mb, pinned_arena, seal, h_arena, descs, part[k].data(), plan[k],
-                                           h_nonces, aad_len, h_status, &bad[k]);
+                                           h_nonces, gen, aad_len, h_status, &bad[k]);
                     return;
                 }
             }
             {  // a worker-sized share of an interleaved batch: in place, as by DMA runs above
                 int drc = QGCM_OK;
                 if (run_member_direct(mb, pinned_arena, seal, h_arena, descs, part[k].data(), part[k].size(),
-                                      h_nonces, aad_len, h_status, &bad[k], &drc)) {
+                                      h_nonces, gen, aad_len, h_status, &bad[k], &drc)) {
                     used_zc[k] = 0;
                     rc[k] = drc;
                     return;
@@ -850,9 +861,9 @@ int run_group(qgcm_group *g, bool seal, uint8_t *h_arena, const qgcm_desc *descs
             }
             used_zc[k] = va ? 1 : 0;
             mb.last_path = va ? 1 : 0;
-            rc[k] = va ? run_member_zc(mb, seal, va, descs, part[k].data(), part[k].size(), vn, aad_len, h_status,
+            rc[k] = va ? run_member_zc(mb, seal, va, descs, part[k].data(), part[k].size(), vn, gen, aad_len, h_status,
                                        &bad[k], g->zc_chunk)
-                       : run_member(mb, seal, h_arena, descs, part[k].data(), part[k].size(), h_nonces, aad_len,
+                       : run_member(mb, seal, h_arena, descs, part[k].data(), part[k].size(), h_nonces, gen, aad_len,
                                     h_status, &bad[k]);
         };
         if (!inline_one) {
@@ -874,7 +885,7 @@ int run_group(qgcm_group *g, bool seal, uint8_t *h_arena, const qgcm_desc *descs
         } else {
             mb.last_path = 2;
             used_zc[k] = 0;
-            rc[k] = run_member_dma(g, mb, pinned_arena, seal, h_arena, descs, part[k].data(), plan[k], h_nonces,
+            rc[k] = run_member_dma(g, mb, pinned_arena, seal, h_arena, descs, part[k].data(), plan[k], h_nonces, gen,
                                    aad_len, h_status, &bad[k]);
         }
         if (had) hipSetDevice(dev0);  // the caller's current device, as it was

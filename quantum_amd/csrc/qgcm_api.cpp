@@ -142,6 +142,10 @@ struct qgcm_ctx {
     uint32_t pool_sets = kPoolSets;  // sets in use (QGCM_POOL_SETS: a short ring, so tests reach the wait)
     std::mutex pool_mu;
 
+    // the nonce generator (nonce_rng.h): qgcm_nonce_fill and QGCM_NONCES_GENERATE reserve from it; its
+    // reseed interval is QGCM_NONCE_RESEED, read at qgcm_create
+    qgcm::NonceRng rng;
+
     std::atomic<uint64_t> launches[QGCM_KERNEL_COUNTERS] = {};  // qgcm_launch_counts
     void count(int k, uint64_t v = 1) { launches[k].fetch_add(v, std::memory_order_relaxed); }
 
@@ -233,8 +237,38 @@ Batch base_batch(const qgcm_ctx *ctx) {
     return b;
 }
 
+// lease / lease_pos (nonces == QGCM_NONCES_GENERATE only): the caller's reservation and this batch's first
+// position in it (qgcm_seal_host's chunks); NULL: the batch reserves its own n positions
 int run_uniform(qgcm_ctx *ctx, bool seal, uint8_t *arena, uint64_t stride, uint32_t n, uint32_t len,
-                uint32_t key_idx, const uint8_t *nonces, uint32_t aad_len, uint8_t *status, hipStream_t s);
+                uint32_t key_idx, const uint8_t *nonces, uint32_t aad_len, uint8_t *status, hipStream_t s,
+                const NonceLease *lease = nullptr, uint64_t lease_pos = 0);
+
+// QGCM_NONCES_GENERATE is a marker, never an address: every layer tests for it before it looks at the
+// nonce pointer's value, alignment or memory type
+inline bool generate(const uint8_t *nonces) { return nonces == QGCM_NONCES_GENERATE; }
+
+// The kernel that writes lease's nonces, nonce j for packet j, on stream s: into the n * 12 B at `out`
+// (kNonceArray), the uniform slots of the arena `out` (kNonceUniform) or the slots descs names there
+// (kNonceDescs; one: the seal that follows is run_descs_one's).
+int nonce_launch(qgcm_ctx *ctx, NonceDest dest, const NonceLease &l, uint8_t *out, const qgcm_desc *descs,
+                 uint64_t stride, uint32_t len, uint32_t n, bool one, hipStream_t s) {
+    NonceArgs a{};
+    a.keys = l.keys;
+    a.v0 = l.v[0];
+    a.v1 = l.v[1];
+    a.v2 = l.v[2];
+    a.v3 = l.v[3];
+    a.out = out;
+    a.descs = descs;
+    a.key_valid = ctx->d_key_valid;
+    a.te = ctx->d_te;
+    a.stride = stride;
+    a.len = len;
+    a.n = n;
+    a.max_keys = ctx->max_keys;
+    a.one = one ? 1u : 0u;
+    return hip_fail(launch_nonce_fill(dest, a, ctx->num_cus, s));
+}
 
 // seal_one / open_one: the latency kernel when the slot fits its LDS staging area, else the batch
 // kernel on a batch of one (QGCM_ONE_KERNEL=0 forces the latter, for A/B runs).
@@ -331,6 +365,13 @@ int qgcm::run_descs_one(qgcm_ctx *ctx, bool seal, uint8_t *d_arena, const qgcm_d
         ((uintptr_t)d_arena & 15))
         return QGCM_E_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    if (seal && generate(d_nonces)) {  // nonce j into descs[j]'s slot, then "the nonce is in the slot"
+        NonceLease l;
+        if (!ctx->rng.reserve(n, l)) return QGCM_E_NOMEM;
+        const int rc = nonce_launch(ctx, kNonceDescs, l, d_arena, d_descs, 0, 0, n, true, s);
+        if (rc != QGCM_OK) return rc;
+        d_nonces = nullptr;
+    }
     Batch b = base_batch(ctx);
     b.arena = d_arena;
     b.descs = d_descs;
@@ -347,15 +388,30 @@ int qgcm::run_descs_one(qgcm_ctx *ctx, bool seal, uint8_t *d_arena, const qgcm_d
 namespace {
 
 int run_uniform(qgcm_ctx *ctx, bool seal, uint8_t *arena, uint64_t stride, uint32_t n, uint32_t len,
-                uint32_t key_idx, const uint8_t *nonces, uint32_t aad_len, uint8_t *status, hipStream_t s) {
+                uint32_t key_idx, const uint8_t *nonces, uint32_t aad_len, uint8_t *status, hipStream_t s,
+                const NonceLease *lease, uint64_t lease_pos) {
+    const bool gen = seal && generate(nonces);
     if (!ctx || (!arena && n) || aad_len > 4 || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
-    if (((uintptr_t)arena & 3) || (stride & 3) || (nonces && ((uintptr_t)nonces & 3))) return QGCM_E_ARG;
+    if (((uintptr_t)arena & 3) || (stride & 3) || (!gen && nonces && ((uintptr_t)nonces & 3))) return QGCM_E_ARG;
     if (n && stride < (uint64_t)len + 4 + (seal ? QGCM_OVERHEAD : 0)) return QGCM_E_ARG;
     if ((seal || len >= QGCM_OVERHEAD) && len - (seal ? 0u : (uint32_t)QGCM_OVERHEAD) >= QGCM_MAX_PAYLOAD)
         return QGCM_E_ARG;
     if (!key_ok(ctx, key_idx)) return QGCM_E_KEY;
     if (n == 0) return QGCM_OK;
     if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    if (gen) {
+        // every check above has passed: reserve (unless the caller did), write nonce j into slot j on
+        // this stream, and seal in "nonce already in the slot" mode, chunked or not
+        NonceLease own;
+        if (!lease) {
+            if (!ctx->rng.reserve(n, own)) return QGCM_E_NOMEM;
+        } else {
+            own = lease_at(*lease, lease_pos);
+        }
+        const int rc = nonce_launch(ctx, kNonceUniform, own, arena, nullptr, stride, len, n, false, s);
+        if (rc != QGCM_OK) return rc;
+        nonces = nullptr;
+    }
     Batch b = base_batch(ctx);
     b.arena = arena;
     b.nonces = seal ? nonces : nullptr;
@@ -420,9 +476,19 @@ int run_descs_locked(qgcm_ctx *ctx, bool seal, const qgcm_desc *descs, uint32_t 
 int run_descs(qgcm_ctx *ctx, bool seal, uint8_t *arena, const qgcm_desc *descs, uint32_t n, const uint8_t *nonces,
               uint32_t aad_len, uint8_t *status, hipStream_t s) {
     if (!ctx || (n && (!arena || !descs)) || aad_len > 4 || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
-    if (((uintptr_t)arena & 3) || (nonces && ((uintptr_t)nonces & 3))) return QGCM_E_ARG;
+    const bool gen = seal && generate(nonces);
+    if (((uintptr_t)arena & 3) || (!gen && nonces && ((uintptr_t)nonces & 3))) return QGCM_E_ARG;
     if (n == 0) return QGCM_OK;
     if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    if (gen) {
+        // nonce j for packet j of the call, written before any chunking below; packets the seal will
+        // reject keep their slots (and their stream positions)
+        NonceLease l;
+        if (!ctx->rng.reserve(n, l)) return QGCM_E_NOMEM;
+        const int rc = nonce_launch(ctx, kNonceDescs, l, arena, descs, 0, 0, n, false, s);
+        if (rc != QGCM_OK) return rc;
+        nonces = nullptr;
+    }
     // statuses start at 0 (packets left out of the worklist keep it); small batches' worklist kernel
     // zeroes them itself
     if (status && !small_worklist(n, ctx->small_wl) && hipMemsetAsync(status, 0, n, s) != hipSuccess) return QGCM_E_HIP;
@@ -690,6 +756,8 @@ qgcm_ctx *qgcm_create(int device, uint32_t max_keys, char *err, int errlen) {
     if (const char *v = getenv("QGCM_DESC_CHUNK")) ctx->desc_chunk = (uint32_t)std::max(0, atoi(v));
     if (const char *v = getenv("QGCM_PIPE_CHUNK_MB")) ctx->host_chunk = (uint64_t)std::max(1, atoi(v)) << 20;
     if (const char *v = getenv("QGCM_PIPE_RING_MB")) ctx->host_ring = (uint64_t)std::max(1, atoi(v)) << 20;
+    if (const char *v = getenv("QGCM_NONCE_RESEED"))  // nonces per generator key (nonce_rng.h; at least 1)
+        ctx->rng.set_interval(std::max<uint64_t>(1, strtoull(v, nullptr, 0)));
     if (const char *v = getenv("QGCM_DESC_VARIANT")) {
         const int iv = atoi(v);
         if (variant_valid(iv) && variant_desc(iv)) ctx->desc_variant = iv;
@@ -969,6 +1037,10 @@ static int run_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride,
         return QGCM_E_ARG;
     if (!key_ok(ctx, key_idx)) return QGCM_E_KEY;
     if (n == 0) return 0;
+    // QGCM_NONCES_GENERATE: no nonce array to resolve, align or copy below; the nonces are written into
+    // the slots by a kernel -- over PCIe on the direct path, into the device chunks otherwise
+    const bool gen = seal && generate(h_nonces);
+    if (gen) h_nonces = nullptr;
     std::lock_guard<std::mutex> g(ctx->io_mu);
     if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
     if (n > ctx->hstat_cap) {
@@ -1002,6 +1074,12 @@ static int run_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride,
             b.n_items = (uint32_t)(((uint64_t)n + 63) & ~63ull);
             b.aad_len = aad_len;
             hipStream_t s = ctx->pipe[0];
+            if (gen) {
+                NonceLease l;
+                if (!ctx->rng.reserve(n, l)) return QGCM_E_NOMEM;
+                const int rc = nonce_launch(ctx, kNonceUniform, l, b.arena, nullptr, stride, len, n, false, s);
+                if (rc != QGCM_OK) return rc;
+            }
             if (launch_one(seal, b, s) != hipSuccess) return QGCM_E_HIP;
             ctx->count(QGCM_KERNEL_ONE);
             if (hipStreamSynchronize(s) != hipSuccess) return QGCM_E_HIP;
@@ -1061,6 +1139,9 @@ static int run_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride,
     int rc = QGCM_OK;
     if (non && hipMemcpyAsync(d_non_all, h_nonces, 12ull * n, hipMemcpyHostToDevice, s_in) != hipSuccess)
         rc = QGCM_E_HIP;
+    // one reservation for the whole call (one key, packet j at position j); chunk c writes its part
+    NonceLease lease;
+    if (gen && !ctx->rng.reserve(n, lease)) return QGCM_E_NOMEM;
     for (uint64_t c = 0; c < nchunks && rc == QGCM_OK; ++c) {
         const int k = (int)(c % nslots);
         uint8_t *d = ctx->d_ring + k * slot;
@@ -1076,8 +1157,9 @@ static int run_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride,
         if (!seal && len < QGCM_OVERHEAD)
             rc = hip_fail(hipMemsetAsync(d_stat_all + c0, 0, cn, s_k));
         else
-            rc = run_uniform(ctx, seal, d, stride, (uint32_t)cn, len, key_idx, non ? d_non_all + 12 * c0 : nullptr,
-                             aad_len, d_stat_all + c0, s_k);
+            rc = run_uniform(ctx, seal, d, stride, (uint32_t)cn, len, key_idx,
+                             gen ? QGCM_NONCES_GENERATE : non ? d_non_all + 12 * c0 : nullptr, aad_len,
+                             d_stat_all + c0, s_k, gen ? &lease : nullptr, c0);
         if (rc == QGCM_OK &&
             (!link(ctx->ev_kern[k], s_k, s_out) ||
              hipMemcpyAsync(h, d, cn * stride, hipMemcpyDeviceToHost, s_out) != hipSuccess ||
@@ -1519,6 +1601,8 @@ int qgcm_chain_codec(qgcm_ctx *ctx, int mode) {
 int qgcm_compress_seal_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *lens,
                             uint32_t key_idx, const uint8_t *h_nonces, uint32_t aad_len, int threads,
                             uint8_t *h_status) {
+    // the chain has no generated-nonce form: refused before anything is touched
+    if (generate(h_nonces)) return QGCM_E_ARG;
     return run_host_chain(ctx, true, h_arena, stride, n, lens, key_idx, h_nonces, aad_len, threads, h_status);
 }
 
@@ -1559,6 +1643,20 @@ int qgcm_random_nonces(uint8_t *h_out, uint32_t n) {
         left -= (size_t)r;
     }
     return QGCM_OK;
+}
+
+int qgcm_nonce_fill(qgcm_ctx *ctx, uint8_t *d_out, uint32_t n, void *stream) {
+    if (!ctx || (n && !d_out) || ((uintptr_t)d_out & 3) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
+    if (n == 0) return QGCM_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    NonceLease l;
+    if (!ctx->rng.reserve(n, l)) return QGCM_E_NOMEM;
+    return nonce_launch(ctx, kNonceArray, l, d_out, nullptr, 0, 0, n, false, (hipStream_t)stream);
+}
+
+int qgcm_nonce_seed(qgcm_ctx *ctx, const uint8_t key[32], const uint8_t counter[16]) {
+    if (!ctx || (key && !counter)) return QGCM_E_ARG;
+    return ctx->rng.seed(key, counter) ? QGCM_OK : QGCM_E_NOMEM;
 }
 
 int qgcm_fill_uniform(uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t len, uint32_t aad_word,

@@ -156,7 +156,9 @@ class Group:
         return _lib.check(rc, "qgcm_group_seal_host" if seal else "qgcm_group_open_host")
 
     def seal_host(self, arena_ptr: int, descs, n: int, nonces_ptr=None, aad_len: int = 4, status_ptr=None) -> int:
-        """descs: numpy structured/uint8 array of qgcm_desc records (host).  Returns failed packets."""
+        """descs: numpy structured/uint8 array of qgcm_desc records (host).  nonces_ptr: a host address
+        (n * 12 B), None (the nonce is in the slot) or _lib.NONCES_GENERATE (each member draws its packets'
+        nonces on its GPU).  Returns failed packets."""
         return self._run(True, arena_ptr, descs, n, nonces_ptr, aad_len, status_ptr)
 
     def open_host(self, arena_ptr: int, descs, n: int, aad_len: int = 4, status_ptr=None) -> int:
