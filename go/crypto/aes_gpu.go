@@ -24,7 +24,9 @@
 //
 // Encrypt / Decrypt are one packet per call (worker/outgoing.go:83-93 calls Apply per packet), served
 // by libqgcm's resident kernel with no launch per call.  Batched workers use the extra API below
-// (Devices, GPUGroup.Order / SealBatch / OpenBatch, Arena, Desc; INTEGRATION.md s2).
+// (Devices, GPUGroup.Order / SealBatch / OpenBatch, Arena, Desc; INTEGRATION.md s2).  A datastore sync
+// that builds many peers' AES objects at once uses NewAESBatch (extra API too): the keys are derived on
+// the GPUs.
 //
 // Differences from crypto/aes.go, all where the reference would panic:
 //   - Encrypt with length < 0 or len(data) < length + 28 returns (-1, errShortBuffer);
@@ -55,6 +57,7 @@ import (
 	"fmt"
 	"os"
 	"runtime"
+	"sort"
 	"strconv"
 	"strings"
 	"sync"
@@ -277,6 +280,100 @@ func (gg *GPUGroup) NewAES(secret, salt []byte) (*AES, error) {
 	a := &AES{g: gg, ctx: ctx, idx: idx, salt: salt}
 	runtime.SetFinalizer(a, func(a *AES) { a.g.release(a.idx) })
 	return a, nil
+}
+
+// NewAESBatch is NewAES for a whole peer table: pair i of secrets / salts becomes AES i of the result.
+// A datastore sync that parses every node's mapping (datastore/etcdv3.go:66-87, etcdv2.go:210-230) collects
+// the (secret, salt) pairs ParseMapping would hand to NewAES one by one (common/mapping.go:90-99) and makes
+// one call: the keys are derived on the GPUs, one key per lane (qgcm_group_derive_set_keys), each GPU
+// derives its own peers' keys and installs them in one pass, and on that path no key byte comes back to
+// the host.  Below QGCM_KDF_DEVICE_MIN keys per GPU (default 576) libqgcm derives on the host instead; a
+// single key is always faster through NewAES.  Every secret and salt must be 32 bytes (an X25519 output,
+// crypto/ecdh.go:23-31); NewAES serves other lengths.  The slots are allocated as NewAES allocates them
+// (recycled ones first) and each AES gets the same finalizer.  On an error no AES is returned and the
+// slots go back to the group; GPUs that had finished hold keys in slots that are marked unset again.
+func NewAESBatch(secrets, salts [][]byte) ([]*AES, error) {
+	gg, err := Devices()
+	if err != nil {
+		return nil, err
+	}
+	return gg.NewAESBatch(secrets, salts)
+}
+
+// NewAESBatch: see the package-level NewAESBatch.
+func (gg *GPUGroup) NewAESBatch(secrets, salts [][]byte) ([]*AES, error) {
+	n := len(secrets)
+	if n != len(salts) {
+		return nil, errors.New("qgcm: secrets and salts differ in number")
+	}
+	for i := 0; i < n; i++ {
+		if len(secrets[i]) != C.QGCM_KEY_BYTES || len(salts[i]) != SaltLength {
+			return nil, errors.New("qgcm: NewAESBatch takes 32-byte secrets and salts")
+		}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	gg.mu.Lock()
+	idx := make([]uint32, 0, n)
+	for len(idx) < n && len(gg.free) > 0 {
+		idx = append(idx, gg.free[len(gg.free)-1])
+		gg.free = gg.free[:len(gg.free)-1]
+	}
+	for len(idx) < n && gg.next < gg.max {
+		idx = append(idx, gg.next)
+		gg.next++
+	}
+	gg.mu.Unlock()
+	giveBack := func() {
+		for _, k := range idx {
+			gg.release(k)
+		}
+	}
+	if len(idx) < n {
+		giveBack()
+		return nil, errSlots
+	}
+	// pair i takes the i-th smallest slot, so that consecutive slots are consecutive pairs: one C call
+	// per run of consecutive slots (a table installed into fresh slots is one run)
+	sort.Slice(idx, func(a, b int) bool { return idx[a] < idx[b] })
+	sec := make([]byte, 0, 32*n)
+	slt := make([]byte, 0, 32*n)
+	for i := 0; i < n; i++ {
+		sec = append(sec, secrets[i]...)
+		slt = append(slt, salts[i]...)
+	}
+	defer func() {
+		for i := range sec {
+			sec[i] = 0
+		}
+	}()
+	for lo := 0; lo < n; {
+		hi := lo + 1
+		for hi < n && idx[hi] == idx[hi-1]+1 {
+			hi++
+		}
+		rc := C.qgcm_group_derive_set_keys(gg.grp, C.uint32_t(idx[lo]), C.uint32_t(hi-lo), bytePtr(sec[32*lo:32*hi]),
+			bytePtr(slt[32*lo:32*hi]))
+		if rc != C.QGCM_OK {
+			giveBack()
+			return nil, errors.New(C.GoString(C.qgcm_strerror(rc)))
+		}
+		lo = hi
+	}
+	out := make([]*AES, n)
+	for i := 0; i < n; i++ {
+		ctx := C.qgcm_group_ctx(gg.grp, C.qgcm_group_shard(gg.grp, C.uint32_t(idx[i])))
+		if ctx == nil {
+			giveBack()
+			return nil, errors.New("qgcm: no owner context")
+		}
+		out[i] = &AES{g: gg, ctx: ctx, idx: idx[i], salt: salts[i]}
+	}
+	for _, a := range out {
+		runtime.SetFinalizer(a, func(a *AES) { a.g.release(a.idx) })
+	}
+	return out, nil
 }
 
 // release marks the slot's key unset on its owner before the slot is reused, so a KeyIndex kept in a

@@ -93,6 +93,30 @@ int qgcm_derive_keys(const uint8_t *secrets, const uint8_t *salts, uint32_t coun
  * tables on the device for slot key_idx.  Synchronous. */
 int qgcm_set_key(qgcm_ctx *ctx, uint32_t key_idx, const uint8_t key[QGCM_KEY_BYTES]);
 int qgcm_set_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, const uint8_t *keys);
+/* ---- peer keys derived on the GPU (batched NewAES; DESIGN.md "Peer keys derived on the GPU") ---- */
+/* keys[i] = PBKDF2-HMAC-SHA512(secrets[i], salts[i], iters, 32) for count 32-byte secrets and salts, derived
+ * on ctx's GPU; host arrays in and out; the same bytes as qgcm_derive_keys when iters = QGCM_PBKDF2_ITERS.
+ * iters in [1, 2^20].  Synchronous.  One key per GPU lane: a key takes longer than on a CPU core, a table
+ * of a few hundred keys or more takes less than on all of them.  Errors in this order: NULL ctx, or a NULL
+ * array with count > 0: QGCM_E_ARG; count 0: QGCM_OK; iters out of range: QGCM_E_ARG (keys untouched). */
+int qgcm_derive_keys_device(qgcm_ctx *ctx, const uint8_t *secrets, const uint8_t *salts, uint32_t count,
+                            uint32_t iters, uint8_t *keys);
+/* NewAES for a whole peer table: derives count keys (QGCM_PBKDF2_ITERS) and installs key i in slot
+ * first_idx + i.  Argument errors as qgcm_set_keys (QGCM_E_ARG, then QGCM_E_KEY for first_idx + count >
+ * max_keys with nothing derived or installed, then QGCM_OK for count 0).  Derives on the GPU when count >=
+ * QGCM_KDF_DEVICE_MIN (environment, read at qgcm_create: 0 = never, 1 = always; default 576), else with
+ * qgcm_derive_keys on the host; both install the same bytes.  On the device path the key bytes never come
+ * back to the host.  The derivation holds none of the context's I/O locks (it runs on a stream of its own,
+ * created by the first device derivation; derivations of one context are serialised): seals, opens and
+ * per-packet calls on keys already installed go on meanwhile.  The install that follows is one pass like
+ * qgcm_set_keys: synchronous, ends the resident instance once. */
+int qgcm_derive_set_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, const uint8_t *secrets,
+                         const uint8_t *salts);
+/* {keys derived on the device, keys derived on the host by qgcm_derive_set_keys, KDF kernel launches,
+ *  install passes}; writes min(n, 4) values, returns that number or -1.  An install pass is one locked
+ *  update of the key tables: every qgcm_set_key(s) call is one, and so is every qgcm_derive_set_keys. */
+int qgcm_kdf_stats(const qgcm_ctx *ctx, uint64_t *out, int n);
+
 /* Marks key slots [first_idx, first_idx + count) unset (the slot's AES was released: go/crypto/aes_gpu.go's
  * finalizer, crypto::DeviceSet::Release).  Afterwards every call naming one of them fails as for a key never
  * set (per-packet calls -1 / QGCM_E_KEY, descriptor batches status 0) until qgcm_set_key(s) installs a new
@@ -205,6 +229,13 @@ int qgcm_group_member_cpus(const qgcm_group *g, int member);
 int qgcm_group_shard(const qgcm_group *g, uint32_t key_idx);
 /* Installs keys[i] as key first_idx + i on its owning member only (qgcm_set_keys there). */
 int qgcm_group_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t *keys);
+/* qgcm_derive_set_keys over the group: each member gets the secrets and salts of the key indices it owns
+ * (qgcm_group_shard), all members derive at once (one host thread each; device or host by each member's
+ * own share and threshold), and each installs its keys in ONE pass, however its indices are scattered
+ * (qgcm_group_set_keys makes one qgcm_set_keys call per run of consecutive indices).  Returns the first
+ * member's error; members that finished keep the keys they installed. */
+int qgcm_group_derive_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t *secrets,
+                               const uint8_t *salts);
 /* qgcm_clear_keys on the owning member of each key index. */
 int qgcm_group_clear_keys(qgcm_group *g, uint32_t first_idx, uint32_t count);
 /* Host batches over the group: packet i is the Raw slot at h_arena + h_descs[i].offset (seal: len = L,

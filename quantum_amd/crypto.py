@@ -104,6 +104,22 @@ class Context:
         _lib.check(_lib.lib().qgcm_set_keys(self.handle, first, len(keys) // keyLength, keys), "qgcm_set_keys")
         self._reserve(first + len(keys) // keyLength)
 
+    def derive_set_keys(self, first: int, secrets: bytes, salts: bytes) -> None:
+        """NewAES for a whole peer table (qgcm_derive_set_keys): key i = PBKDF2(secrets[i], salts[i]) goes
+        into slot first + i, derived on the GPU from QGCM_KDF_DEVICE_MIN keys on (there the key bytes never
+        reach the host), installed in one pass.  secrets / salts: count * 32 bytes each."""
+        n = _kdf_count(secrets, salts)
+        _lib.check(_lib.lib().qgcm_derive_set_keys(self.handle, first, n, secrets, salts), "qgcm_derive_set_keys")
+        self._reserve(first + n)
+
+    def kdf_stats(self) -> dict:
+        """Keys derived on the device, keys derived on the host by derive_set_keys, KDF kernel launches,
+        install passes (every set_key(s) and derive_set_keys call is one) -- qgcm_kdf_stats."""
+        names = ("device_keys", "host_keys", "launches", "install_passes")
+        out = (C.c_uint64 * len(names))()
+        n = _lib.check(_lib.lib().qgcm_kdf_stats(self.handle, out, len(names)), "qgcm_kdf_stats")
+        return dict(zip(names[:n], (int(x) for x in out)))
+
     def clear_keys(self, first: int, count: int = 1) -> None:
         """qgcm_clear_keys: slots [first, first + count) unset (their AES was released); calls naming
         them fail until a key is set there again."""
@@ -148,6 +164,22 @@ def derive_keys(secrets: bytes, salts: bytes) -> bytes:
         raise ValueError("secrets/salts must be count*32 bytes")
     out = C.create_string_buffer(32 * n)
     _lib.check(_lib.lib().qgcm_derive_keys(secrets, salts, n, out), "qgcm_derive_keys")
+    return out.raw
+
+
+def _kdf_count(secrets: bytes, salts: bytes) -> int:
+    n = len(secrets) // 32
+    if len(secrets) != 32 * n or len(salts) != 32 * n:
+        raise ValueError("secrets/salts must be count*32 bytes")
+    return n
+
+
+def derive_keys_device(ctx: Context, secrets: bytes, salts: bytes, iters: int = iterations) -> bytes:
+    """derive_keys on ctx's GPU, one key per lane (qgcm_derive_keys_device): the same bytes for
+    iters = 10000; iters in [1, 2^20]."""
+    n = _kdf_count(secrets, salts)
+    out = C.create_string_buffer(32 * n)
+    _lib.check(_lib.lib().qgcm_derive_keys_device(ctx.handle, secrets, salts, n, iters, out), "qgcm_derive_keys_device")
     return out.raw
 
 

@@ -248,6 +248,27 @@ hipError_t launch_pw_setup(uint32_t first, uint32_t count, const uint4 *gh_table
                            hipStream_t s);
 hipError_t launch_key_setup(const uint8_t *d_keys, uint32_t first, uint32_t count, uint32_t *rk_table,
                             uint4 *gh_table, const uint8_t *d_sbox, hipStream_t s);
+// Peer keys on the device (kdf_kernels.hip, kdf_core.h): d_keys[i] = PBKDF2-HMAC-SHA512(d_secrets[i],
+// d_salts[i], iters, 32), 32 B each, 4-B aligned, one key per lane of kdf_pbkdf2_kernel.  One launch covers at
+// most kKdfLaunchKeys keys (two waves per SIMD on 256 CUs), more go as successive launches on s, so a
+// kernel's run time stays near one key's latency whatever the count.  iters in [1, 2^20];
+// *launches (may be NULL): kernels enqueued.
+constexpr uint32_t kKdfLaunchKeys = 1u << 17;
+hipError_t launch_kdf(const uint8_t *d_secrets, const uint8_t *d_salts, uint32_t count, uint32_t iters, uint8_t *d_keys,
+                      hipStream_t s, uint32_t *launches);
+constexpr uint32_t kKdfDeviceMin = 576;  // qgcm_derive_set_keys derives on the device from this many keys on
+                                         // (QGCM_KDF_DEVICE_MIN at qgcm_create; DESIGN.md "Peer keys derived on the GPU")
+// Key slots [first, first + count) take keys src, src + 1, ... of a device key buffer.
+struct KeyRun {
+    uint32_t first, count, src;
+};
+// qgcm_api.cpp: one install pass over several runs of slots (qgcm_set_keys is the one-run caller), and
+// derive-then-install for a member's share of a peer table (qgcm_derive_set_keys, group.cpp).  The callers
+// check the runs against ctx_max_keys.
+int install_device_keys(qgcm_ctx *ctx, const KeyRun *runs, size_t nruns, uint8_t *d_keys, uint32_t key_count,
+                        const uint8_t *h_src);
+int derive_install_runs(qgcm_ctx *ctx, const KeyRun *runs, size_t nruns, uint32_t count, const uint8_t *secrets,
+                        const uint8_t *salts);
 hipError_t launch_fill_uniform(uint8_t *arena, uint64_t stride, uint32_t n, uint32_t len, uint32_t aad_word,
                                uint64_t seed_payload, uint8_t *nonces, uint64_t seed_nonce, hipStream_t s);
 

@@ -1024,6 +1024,49 @@ int qgcm_group_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const
     return QGCM_OK;
 }
 
+int qgcm_group_derive_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t *secrets,
+                               const uint8_t *salts) {
+    if (!g || g->m.empty() || (count && (!secrets || !salts))) return QGCM_E_ARG;
+    if ((uint64_t)first_idx + count > g->max_keys) return QGCM_E_KEY;
+    if (count == 0) return QGCM_OK;
+    // each member's share: its secrets and salts gathered in index order, and the runs of consecutive
+    // slots they fill
+    const int G = (int)g->m.size();
+    struct Share {
+        std::vector<uint8_t> secrets, salts;
+        std::vector<qgcm::KeyRun> runs;
+        uint32_t count = 0;
+    };
+    std::vector<Share> sh(G);
+    for (uint32_t i = 0; i < count; ++i) {
+        Share &x = sh[qgcm_group_shard(g, first_idx + i)];
+        x.secrets.insert(x.secrets.end(), secrets + 32ull * i, secrets + 32ull * i + 32);
+        x.salts.insert(x.salts.end(), salts + 32ull * i, salts + 32ull * i + 32);
+        if (!x.runs.empty() && x.runs.back().first + x.runs.back().count == first_idx + i) ++x.runs.back().count;
+        else x.runs.push_back({first_idx + i, 1, x.count});
+        ++x.count;
+    }
+    // one host thread per member with a share: derivation (device or host by the member's own threshold)
+    // and one install pass each, all members at once
+    std::vector<int> rc(G, QGCM_OK);
+    std::vector<std::thread> thr;
+    for (int k = 0; k < G; ++k) {
+        if (!sh[k].count) continue;
+        thr.emplace_back([&, k] {
+            rc[k] = qgcm::derive_install_runs(g->m[k].ctx, sh[k].runs.data(), sh[k].runs.size(), sh[k].count,
+                                              sh[k].secrets.data(), sh[k].salts.data());
+        });
+    }
+    for (auto &t : thr) t.join();
+    for (Share &x : sh) {
+        if (!x.secrets.empty()) explicit_bzero(x.secrets.data(), x.secrets.size());
+        if (!x.salts.empty()) explicit_bzero(x.salts.data(), x.salts.size());
+    }
+    for (int k = 0; k < G; ++k)
+        if (rc[k] != QGCM_OK) return rc[k];  // the first error; members that finished keep their keys
+    return QGCM_OK;
+}
+
 int qgcm_group_clear_keys(qgcm_group *g, uint32_t first_idx, uint32_t count) {
     if (!g) return QGCM_E_ARG;
     if ((uint64_t)first_idx + count > g->max_keys) return QGCM_E_KEY;

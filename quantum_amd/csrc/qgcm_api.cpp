@@ -24,6 +24,7 @@
 #include "../../include/qgcm.h"
 #include "chain_claim.h"
 #include "gcm_internal.h"
+#include "kdf_core.h"
 
 using namespace qgcm;
 
@@ -159,6 +160,16 @@ struct qgcm_ctx {
     std::atomic<qgcm::Resident *> res{nullptr};
     std::atomic<bool> res_failed{false};
     std::mutex res_mu;
+
+    // peer keys derived on the device (qgcm_derive_keys_device, qgcm_derive_set_keys; kdf_kernels.hip).
+    // Derivations run on a stream of their own, created by the first one, and are serialised by kdf_mu;
+    // they take neither io_mu nor res_mu, so traffic on installed keys goes on meanwhile.
+    uint32_t kdf_device_min = kKdfDeviceMin;  // QGCM_KDF_DEVICE_MIN: 0 never the device, 1 always
+    std::mutex kdf_mu;
+    hipStream_t kdf_stream = nullptr;
+    // keys derived on the device, keys derived on the host by qgcm_derive_set_keys, KDF kernel launches,
+    // install passes (qgcm_kdf_stats)
+    std::atomic<uint64_t> kdf_stats[4] = {};
 };
 
 namespace {
@@ -670,6 +681,119 @@ static std::shared_future<std::vector<int>> codec_cpu_list(int device) {
     return l.ready.valid() ? l.ready : l.next;
 }
 
+// One install pass (the body of qgcm_set_keys): expands the round keys and GHASH tables of every run from
+// d_keys (32 B per key; run r's keys start at key number runs[r].src) on the context's kernel stream.
+// The locks are taken once, the resident instance is paused once and the stream is synchronised once,
+// however many runs there are.  h_src (may be NULL): key_count keys copied into d_keys first, on the same
+// stream.  d_keys is zeroed behind the last reader, so the caller frees a buffer that holds no key.
+int qgcm::install_device_keys(qgcm_ctx *ctx, const KeyRun *runs, size_t nruns, uint8_t *d_keys, uint32_t key_count,
+                              const uint8_t *h_src) {
+    // The key setup runs on the context's kernel stream (no stream created per call: every stream a
+    // process creates moves HIP's stream -> hardware-queue assignment on, and two pipeline stages that
+    // end up on one hardware queue serialize their copies).
+    std::lock_guard<std::mutex> io(ctx->io_mu);
+    hipStream_t s = ctx->pipe[1];
+    // a running resident instance holds key tables (and keystreams computed ahead, key-valid bytes) in
+    // its caches: end it BEFORE the tables change and start no new one until the new keys are published.
+    // res_mu is held for the whole update, so a per-packet call that finds no service cannot create one
+    // meanwhile (get_resident takes res_mu to create; an instance created mid-update would cache the
+    // tables being rewritten, and nothing would end it)
+    std::lock_guard<std::mutex> res_lk(ctx->res_mu);
+    Resident *res = ctx->res.load(std::memory_order_acquire);
+    (void)resident_pause(res);  // a failure marks the resident path broken: calls take the launch path
+    ctx->kdf_stats[3].fetch_add(1, std::memory_order_relaxed);
+    int rc = QGCM_OK;
+    if (h_src && hipMemcpyAsync(d_keys, h_src, (size_t)key_count * 32, hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = QGCM_E_HIP;
+    for (size_t r = 0; rc == QGCM_OK && r < nruns; ++r) {
+        const KeyRun &k = runs[r];
+        if (launch_key_setup(d_keys + 32ull * k.src, k.first, k.count, ctx->d_rk, ctx->d_gh, ctx->d_sbox, s) != hipSuccess ||
+            launch_pw_setup(k.first, k.count, ctx->d_gh, ctx->d_pw, ctx->pw_keys, s) != hipSuccess ||
+            hipMemsetAsync(ctx->d_key_valid + k.first, 1, k.count, s) != hipSuccess)
+            rc = QGCM_E_HIP;
+    }
+    // (enqueued even after a failure above, so the key bytes never outlive the call)
+    if (hipMemsetAsync(d_keys, 0, (size_t)key_count * 32, s) != hipSuccess) rc = QGCM_E_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
+    if (rc == QGCM_OK) {
+        std::lock_guard<std::mutex> g(ctx->key_mu);
+        for (size_t r = 0; r < nruns; ++r)
+            for (uint32_t i = 0; i < runs[r].count; ++i)
+                __atomic_store_n(&ctx->key_set[runs[r].first + i], (uint8_t)1, __ATOMIC_RELEASE);
+    }
+    resident_resume(res);  // the next per-packet call starts a fresh instance
+    return rc;
+}
+
+namespace {
+
+// d_keys[i] = PBKDF2(secrets[i], salts[i], iters) for host arrays, on the context's derivation stream;
+// complete on return.  h_out (may be NULL): the keys copied to host memory, and d_keys zeroed behind the
+// copy.  Holds kdf_mu only.
+int kdf_on_device(qgcm_ctx *ctx, const uint8_t *secrets, const uint8_t *salts, uint32_t count, uint32_t iters,
+                  uint8_t *d_keys, uint8_t *h_out) {
+    std::lock_guard<std::mutex> lk(ctx->kdf_mu);
+    if (!ctx->kdf_stream && hipStreamCreateWithFlags(&ctx->kdf_stream, hipStreamNonBlocking) != hipSuccess) {
+        ctx->kdf_stream = nullptr;
+        return QGCM_E_HIP;
+    }
+    hipStream_t s = ctx->kdf_stream;
+    const size_t bytes = (size_t)count * 32;
+    uint8_t *d_in = nullptr;  // secrets, then salts
+    if (hipMalloc(&d_in, 2 * bytes) != hipSuccess) return QGCM_E_NOMEM;
+    uint32_t launches = 0;
+    int rc = QGCM_OK;
+    if (hipMemcpyAsync(d_in, secrets, bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_in + bytes, salts, bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_kdf(d_in, d_in + bytes, count, iters, d_keys, s, &launches) != hipSuccess)
+        rc = QGCM_E_HIP;
+    if (hipMemsetAsync(d_in, 0, 2 * bytes, s) != hipSuccess) rc = QGCM_E_HIP;  // the secrets do not outlive the call
+    if (h_out) {
+        if (rc == QGCM_OK && hipMemcpyAsync(h_out, d_keys, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) rc = QGCM_E_HIP;
+        if (hipMemsetAsync(d_keys, 0, bytes, s) != hipSuccess) rc = QGCM_E_HIP;
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
+    hipFree(d_in);
+    ctx->kdf_stats[2].fetch_add(launches, std::memory_order_relaxed);
+    if (rc == QGCM_OK) ctx->kdf_stats[0].fetch_add(count, std::memory_order_relaxed);
+    return rc;
+}
+
+// enqueue-and-wait wipe of a device key buffer that no install pass has zeroed
+void wipe_device_keys(qgcm_ctx *ctx, uint8_t *d_keys, uint32_t count) {
+    std::lock_guard<std::mutex> lk(ctx->kdf_mu);
+    hipStream_t s = ctx->kdf_stream;  // NULL (never created): the null stream
+    if (hipMemsetAsync(d_keys, 0, (size_t)count * 32, s) == hipSuccess) (void)hipStreamSynchronize(s);
+}
+
+}  // namespace
+
+// NewAES for `count` peers whose slots are the runs (their src fields index secrets / salts): derive on
+// the device at or above the context's threshold, else on the host, then one install pass.
+int qgcm::derive_install_runs(qgcm_ctx *ctx, const KeyRun *runs, size_t nruns, uint32_t count, const uint8_t *secrets,
+                              const uint8_t *salts) {
+    if (count == 0) return QGCM_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    uint8_t *d_keys = nullptr;
+    if (hipMalloc(&d_keys, (size_t)count * 32) != hipSuccess) return QGCM_E_NOMEM;
+    int rc;
+    if (ctx->kdf_device_min && count >= ctx->kdf_device_min) {
+        rc = kdf_on_device(ctx, secrets, salts, count, QGCM_PBKDF2_ITERS, d_keys, nullptr);
+        if (rc == QGCM_OK) rc = install_device_keys(ctx, runs, nruns, d_keys, count, nullptr);
+        else wipe_device_keys(ctx, d_keys, count);
+    } else {
+        std::vector<uint8_t> keys((size_t)count * 32);
+        rc = qgcm_derive_keys(secrets, salts, count, keys.data());
+        if (rc == QGCM_OK) {
+            ctx->kdf_stats[1].fetch_add(count, std::memory_order_relaxed);
+            rc = install_device_keys(ctx, runs, nruns, d_keys, count, keys.data());
+        }
+        explicit_bzero(keys.data(), keys.size());
+    }
+    hipFree(d_keys);
+    return rc;
+}
+
 extern "C" {
 
 const char *qgcm_version(void) { return "qgcm 0.1.0 (gfx950)"; }
@@ -776,6 +900,7 @@ qgcm_ctx *qgcm_create(int device, uint32_t max_keys, char *err, int errlen) {
     ctx->desc_one_on = !off("QGCM_DESC_ONE");
     ctx->host_direct = !off("QGCM_HOST_DIRECT");
     ctx->small_wl = !off("QGCM_SMALL_WORKLIST");
+    ctx->kdf_device_min = (uint32_t)std::max(0, env_int("QGCM_KDF_DEVICE_MIN", (int)kKdfDeviceMin));
     uint8_t sbox[256];
     uint32_t te[512];
     build_tables(sbox, te);
@@ -841,6 +966,7 @@ void qgcm_destroy(qgcm_ctx *ctx) {
     if (ctx->h_desc) hipHostFree(ctx->h_desc);
     if (ctx->h_lens) hipHostFree(ctx->h_lens);
     for (hipStream_t x : ctx->chain_extra) hipStreamDestroy(x);
+    if (ctx->kdf_stream) hipStreamDestroy(ctx->kdf_stream);
     for (hipStream_t p : ctx->pipe)
         if (p) hipStreamDestroy(p);
     if (ctx->ws_done) hipEventDestroy(ctx->ws_done);
@@ -858,37 +984,47 @@ int qgcm_set_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, const uint8
     if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
     uint8_t *d_keys = nullptr;
     if (hipMalloc(&d_keys, (size_t)count * 32) != hipSuccess) return QGCM_E_NOMEM;
-    // The key setup runs on the context's kernel stream (no stream created per call: every stream a
-    // process creates moves HIP's stream -> hardware-queue assignment on, and two pipeline stages that
-    // end up on one hardware queue serialize their copies).
-    std::lock_guard<std::mutex> io(ctx->io_mu);
-    hipStream_t s = ctx->pipe[1];
-    // a running resident instance holds key tables (and keystreams computed ahead, key-valid bytes) in
-    // its caches: end it BEFORE the tables change and start no new one until the new keys are published.
-    // res_mu is held for the whole update, so a per-packet call that finds no service cannot create one
-    // meanwhile (get_resident takes res_mu to create; an instance created mid-update would cache the
-    // tables being rewritten, and nothing would end it)
-    std::lock_guard<std::mutex> res_lk(ctx->res_mu);
-    Resident *res = ctx->res.load(std::memory_order_acquire);
-    (void)resident_pause(res);  // a failure marks the resident path broken: calls take the launch path
-    int rc = QGCM_OK;
-    if (hipMemcpyAsync(d_keys, keys, (size_t)count * 32, hipMemcpyHostToDevice, s) != hipSuccess ||
-        launch_key_setup(d_keys, first_idx, count, ctx->d_rk, ctx->d_gh, ctx->d_sbox, s) != hipSuccess ||
-        launch_pw_setup(first_idx, count, ctx->d_gh, ctx->d_pw, ctx->pw_keys, s) != hipSuccess ||
-        hipMemsetAsync(ctx->d_key_valid + first_idx, 1, count, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess)
-        rc = QGCM_E_HIP;
+    const KeyRun run{first_idx, count, 0};
+    const int rc = install_device_keys(ctx, &run, 1, d_keys, count, keys);
     hipFree(d_keys);
-    if (rc == QGCM_OK) {
-        std::lock_guard<std::mutex> g(ctx->key_mu);
-        for (uint32_t i = 0; i < count; ++i) __atomic_store_n(&ctx->key_set[first_idx + i], (uint8_t)1, __ATOMIC_RELEASE);
-    }
-    resident_resume(res);  // the next per-packet call starts a fresh instance
     return rc;
 }
 
 int qgcm_set_key(qgcm_ctx *ctx, uint32_t key_idx, const uint8_t key[QGCM_KEY_BYTES]) {
     return qgcm_set_keys(ctx, key_idx, 1, key);
+}
+
+int qgcm_derive_keys_device(qgcm_ctx *ctx, const uint8_t *secrets, const uint8_t *salts, uint32_t count, uint32_t iters,
+                            uint8_t *keys) {
+    if (!ctx || (count && (!secrets || !salts || !keys))) return QGCM_E_ARG;
+    if (count == 0) return QGCM_OK;
+    if (iters == 0 || iters > kKdfMaxIters) return QGCM_E_ARG;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    uint8_t *d_keys = nullptr;
+    if (hipMalloc(&d_keys, (size_t)count * 32) != hipSuccess) return QGCM_E_NOMEM;
+    // into a bounce buffer, so that a failed call leaves `keys` untouched
+    std::vector<uint8_t> out((size_t)count * 32);
+    const int rc = kdf_on_device(ctx, secrets, salts, count, iters, d_keys, out.data());
+    hipFree(d_keys);
+    if (rc == QGCM_OK) memcpy(keys, out.data(), out.size());
+    explicit_bzero(out.data(), out.size());
+    return rc;
+}
+
+int qgcm_derive_set_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, const uint8_t *secrets,
+                         const uint8_t *salts) {
+    if (!ctx || (count && (!secrets || !salts))) return QGCM_E_ARG;
+    if ((uint64_t)first_idx + count > ctx->max_keys) return QGCM_E_KEY;
+    if (count == 0) return QGCM_OK;
+    const KeyRun run{first_idx, count, 0};
+    return derive_install_runs(ctx, &run, 1, count, secrets, salts);
+}
+
+int qgcm_kdf_stats(const qgcm_ctx *ctx, uint64_t *out, int n) {
+    if (!ctx || !out || n < 0) return -1;
+    const int m = std::min(n, 4);
+    for (int i = 0; i < m; ++i) out[i] = ctx->kdf_stats[i].load(std::memory_order_relaxed);
+    return m;
 }
 
 int qgcm_clear_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count) {

@@ -146,6 +146,17 @@ class Group:
 
         _lib.check(_lib.lib().qgcm_group_set_keys(self.handle, first, len(keys) // 32, keys), "qgcm_group_set_keys")
 
+    def derive_set_keys(self, first: int, secrets: bytes, salts: bytes) -> None:
+        """qgcm_group_derive_set_keys: key i = PBKDF2(secrets[i], salts[i]) into slot first + i of its owning
+        member; the members derive their shares at once and install them in one pass each."""
+        from . import _lib
+
+        n = len(secrets) // 32
+        if len(secrets) != 32 * n or len(salts) != 32 * n:
+            raise ValueError("secrets/salts must be count*32 bytes")
+        _lib.check(_lib.lib().qgcm_group_derive_set_keys(self.handle, first, n, secrets, salts),
+                   "qgcm_group_derive_set_keys")
+
     def _run(self, seal: bool, arena_ptr: int, descs, n: int, nonces_ptr, aad_len: int, status_ptr) -> int:
         from . import _lib
 
