@@ -26,7 +26,8 @@
 // by libqgcm's resident kernel with no launch per call.  Batched workers use the extra API below
 // (Devices, GPUGroup.Order / SealBatch / OpenBatch, Arena, Desc; INTEGRATION.md s2).  A datastore sync
 // that builds many peers' AES objects at once uses NewAESBatch (extra API too): the keys are derived on
-// the GPUs.
+// the GPUs -- or NewAESPeers, which starts from the peers' public keys and runs the X25519 ladders there
+// as well.
 //
 // Differences from crypto/aes.go, all where the reference would panic:
 //   - Encrypt with length < 0 or len(data) < length + 28 returns (-1, errShortBuffer);
@@ -314,6 +315,27 @@ func (gg *GPUGroup) NewAESBatch(secrets, salts [][]byte) ([]*AES, error) {
 	if n == 0 {
 		return nil, nil
 	}
+	sec := make([]byte, 0, 32*n)
+	slt := make([]byte, 0, 32*n)
+	for i := 0; i < n; i++ {
+		sec = append(sec, secrets[i]...)
+		slt = append(slt, salts[i]...)
+	}
+	defer func() {
+		for i := range sec {
+			sec[i] = 0
+		}
+	}()
+	return gg.newTable(n, salts, func(first uint32, lo, hi int) C.int {
+		return C.qgcm_group_derive_set_keys(gg.grp, C.uint32_t(first), C.uint32_t(hi-lo), bytePtr(sec[32*lo:32*hi]),
+			bytePtr(slt[32*lo:32*hi]))
+	})
+}
+
+// newTable allocates n key slots as NewAES allocates them (recycled ones first), has install fill them --
+// entries [lo, hi) of the caller's table go to the consecutive slots from first on -- and wraps them in AES
+// objects with the usual finalizer.  salts (may be nil) are the objects' salts.
+func (gg *GPUGroup) newTable(n int, salts [][]byte, install func(first uint32, lo, hi int) C.int) ([]*AES, error) {
 	gg.mu.Lock()
 	idx := make([]uint32, 0, n)
 	for len(idx) < n && len(gg.free) > 0 {
@@ -334,28 +356,15 @@ func (gg *GPUGroup) NewAESBatch(secrets, salts [][]byte) ([]*AES, error) {
 		giveBack()
 		return nil, errSlots
 	}
-	// pair i takes the i-th smallest slot, so that consecutive slots are consecutive pairs: one C call
+	// entry i takes the i-th smallest slot, so that consecutive slots are consecutive entries: one C call
 	// per run of consecutive slots (a table installed into fresh slots is one run)
 	sort.Slice(idx, func(a, b int) bool { return idx[a] < idx[b] })
-	sec := make([]byte, 0, 32*n)
-	slt := make([]byte, 0, 32*n)
-	for i := 0; i < n; i++ {
-		sec = append(sec, secrets[i]...)
-		slt = append(slt, salts[i]...)
-	}
-	defer func() {
-		for i := range sec {
-			sec[i] = 0
-		}
-	}()
 	for lo := 0; lo < n; {
 		hi := lo + 1
 		for hi < n && idx[hi] == idx[hi-1]+1 {
 			hi++
 		}
-		rc := C.qgcm_group_derive_set_keys(gg.grp, C.uint32_t(idx[lo]), C.uint32_t(hi-lo), bytePtr(sec[32*lo:32*hi]),
-			bytePtr(slt[32*lo:32*hi]))
-		if rc != C.QGCM_OK {
+		if rc := install(idx[lo], lo, hi); rc != C.QGCM_OK {
 			giveBack()
 			return nil, errors.New(C.GoString(C.qgcm_strerror(rc)))
 		}
@@ -368,12 +377,61 @@ func (gg *GPUGroup) NewAESBatch(secrets, salts [][]byte) ([]*AES, error) {
 			giveBack()
 			return nil, errors.New("qgcm: no owner context")
 		}
-		out[i] = &AES{g: gg, ctx: ctx, idx: idx[i], salt: salts[i]}
+		out[i] = &AES{g: gg, ctx: ctx, idx: idx[i]}
+		if salts != nil {
+			out[i].salt = salts[i]
+		}
 	}
 	for _, a := range out {
 		runtime.SetFinalizer(a, func(a *AES) { a.g.release(a.idx) })
 	}
 	return out, nil
+}
+
+// NewAESPeers is common/mapping.go:90-99 for a whole peer table: peer i's public key and public salt, with
+// this node's private key and private salt, become AES i of the result.  A datastore sync hands over what
+// the datastore holds -- the public values -- and makes one call: the two X25519 shared secrets per peer
+// are computed on the GPUs, one ladder per lane, the keys are derived from them there and installed
+// (qgcm_group_peers_set_keys), and on that path no shared secret, salt or key reaches the host.  Below
+// QGCM_KDF_DEVICE_MIN peers per GPU libqgcm runs the ladders and the derivation on the host instead.  Every
+// value must be 32 bytes.  Like curve25519.ScalarMult of the reference's vintage, nothing is refused: a
+// small-order public value yields the all-zero shared secret.  The objects keep no salt (it never leaves the
+// GPU).  Slots, finalizers and errors as NewAESBatch.
+func NewAESPeers(pubKeys, pubSalts [][]byte, privKey, privSalt []byte) ([]*AES, error) {
+	gg, err := Devices()
+	if err != nil {
+		return nil, err
+	}
+	return gg.NewAESPeers(pubKeys, pubSalts, privKey, privSalt)
+}
+
+// NewAESPeers: see the package-level NewAESPeers.
+func (gg *GPUGroup) NewAESPeers(pubKeys, pubSalts [][]byte, privKey, privSalt []byte) ([]*AES, error) {
+	n := len(pubKeys)
+	if n != len(pubSalts) {
+		return nil, errors.New("qgcm: public keys and public salts differ in number")
+	}
+	if len(privKey) != 32 || len(privSalt) != 32 {
+		return nil, errors.New("qgcm: NewAESPeers takes a 32-byte private key and private salt")
+	}
+	for i := 0; i < n; i++ {
+		if len(pubKeys[i]) != 32 || len(pubSalts[i]) != 32 {
+			return nil, errors.New("qgcm: NewAESPeers takes 32-byte public keys and public salts")
+		}
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	keys := make([]byte, 0, 32*n)
+	slts := make([]byte, 0, 32*n)
+	for i := 0; i < n; i++ {
+		keys = append(keys, pubKeys[i]...)
+		slts = append(slts, pubSalts[i]...)
+	}
+	return gg.newTable(n, nil, func(first uint32, lo, hi int) C.int {
+		return C.qgcm_group_peers_set_keys(gg.grp, C.uint32_t(first), C.uint32_t(hi-lo), bytePtr(privKey), bytePtr(privSalt),
+			bytePtr(keys[32*lo:32*hi]), bytePtr(slts[32*lo:32*hi]))
+	})
 }
 
 // release marks the slot's key unset on its owner before the slot is reused, so a KeyIndex kept in a

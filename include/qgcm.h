@@ -126,6 +126,35 @@ int qgcm_clear_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count);
 /* X25519 (crypto/ecdh.go:13-31): pub = X25519(priv, 9); secret = X25519(priv, peer_pub). */
 int qgcm_x25519_base(uint8_t pub[32], const uint8_t priv[32]);
 int qgcm_x25519(uint8_t secret[32], const uint8_t priv[32], const uint8_t peer_pub[32]);
+/* ---- a peer table keyed from public keys on the GPU (batched X25519; DESIGN.md "Peer secrets computed on
+ * the GPU") ---- */
+/* out[i] = X25519(scalars[i * scalar_stride .. +32), points[i]); scalar_stride 0 (one scalar for all) or 32.
+ * Host, multithreaded like qgcm_derive_keys.  The semantics of qgcm_x25519: the scalar is clamped, bit 255 of
+ * a point is ignored, nothing is refused (a small-order point gives the all-zero output).  A NULL array with
+ * count > 0, or another stride: QGCM_E_ARG. */
+int qgcm_x25519_batch(const uint8_t *scalars, uint32_t scalar_stride, const uint8_t *points, uint32_t count,
+                      uint8_t *out);
+/* The same bytes computed on ctx's GPU, one ladder per lane; host arrays in and out.  Synchronous.  Errors in
+ * this order: NULL ctx, or a NULL array with count > 0: QGCM_E_ARG; another stride: QGCM_E_ARG; count 0:
+ * QGCM_OK.  A failed call leaves out untouched. */
+int qgcm_x25519_device(qgcm_ctx *ctx, const uint8_t *scalars, uint32_t scalar_stride, const uint8_t *points,
+                       uint32_t count, uint8_t *out);
+/* common/mapping.go:90-99 for a table, on ctx's GPU: keys[i] = PBKDF2-HMAC-SHA512(X25519(priv_key,
+ * pub_keys[i]), X25519(priv_salt, pub_salts[i]), QGCM_PBKDF2_ITERS, 32).  One ladder launch over 2 * count
+ * lanes, then the derivation kernel, on the context's derivation stream; only the keys come back.
+ * Synchronous. */
+int qgcm_peer_keys_device(qgcm_ctx *ctx, const uint8_t priv_key[32], const uint8_t priv_salt[32],
+                          const uint8_t *pub_keys, const uint8_t *pub_salts, uint32_t count, uint8_t *keys);
+/* The same, installed in slots first_idx + i.  Argument errors as qgcm_derive_set_keys (NULL: QGCM_E_ARG;
+ * first_idx + count > max_keys: QGCM_E_KEY with nothing computed; count 0: QGCM_OK).  Runs on the GPU when
+ * count >= QGCM_KDF_DEVICE_MIN -- the secrets, salts and keys then never reach the host -- else
+ * qgcm_x25519_batch and qgcm_derive_keys on the host; both install the same bytes.  Locks, the install pass
+ * and the four qgcm_kdf_stats counters are those of qgcm_derive_set_keys for the same count. */
+int qgcm_peers_set_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, const uint8_t priv_key[32],
+                        const uint8_t priv_salt[32], const uint8_t *pub_keys, const uint8_t *pub_salts);
+/* {ladders run on the device, ladders run on the host by qgcm_peers_set_keys, ladder kernel launches};
+ * writes min(n, 3) values, returns that number or -1. */
+int qgcm_ecdh_stats(const qgcm_ctx *ctx, uint64_t *out, int n);
 
 /* ---- device batches (the throughput path) ---- */
 /* Seal n packets in place.  nonces: device array of n*12 bytes (nonce i for packet i, written
@@ -236,6 +265,11 @@ int qgcm_group_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const
  * member's error; members that finished keep the keys they installed. */
 int qgcm_group_derive_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t *secrets,
                                const uint8_t *salts);
+/* qgcm_peers_set_keys over the group: each member gets the public values of the key indices it owns
+ * (qgcm_group_shard), all members work at once (ladders and derivation on each member's GPU or host by its
+ * own threshold), one install pass per member.  Errors as qgcm_group_derive_set_keys. */
+int qgcm_group_peers_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t priv_key[32],
+                              const uint8_t priv_salt[32], const uint8_t *pub_keys, const uint8_t *pub_salts);
 /* qgcm_clear_keys on the owning member of each key index. */
 int qgcm_group_clear_keys(qgcm_group *g, uint32_t first_idx, uint32_t count);
 /* Host batches over the group: packet i is the Raw slot at h_arena + h_descs[i].offset (seal: len = L,

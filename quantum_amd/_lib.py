@@ -21,6 +21,8 @@ EXPORTS = (
     "qgcm_derive_key", "qgcm_derive_keys", "qgcm_set_key", "qgcm_set_keys", "qgcm_clear_keys",
     "qgcm_x25519_base", "qgcm_x25519",
     "qgcm_derive_keys_device", "qgcm_derive_set_keys", "qgcm_kdf_stats", "qgcm_group_derive_set_keys",
+    "qgcm_x25519_batch", "qgcm_x25519_device", "qgcm_peer_keys_device", "qgcm_peers_set_keys", "qgcm_ecdh_stats",
+    "qgcm_group_peers_set_keys",
     "qgcm_seal_batch", "qgcm_open_batch", "qgcm_seal_uniform", "qgcm_open_uniform",
     "qgcm_seal_one", "qgcm_open_one", "qgcm_seal_host", "qgcm_open_host",
     "qgcm_random_nonces", "qgcm_nonce_fill", "qgcm_nonce_seed", "qgcm_fill_uniform", "qgcm_host_alloc", "qgcm_host_free",
@@ -86,6 +88,13 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_derive_set_keys.argtypes = [vp, u32, u32, u8p, u8p]
         L.qgcm_kdf_stats.argtypes = [vp, vp, i32]
         L.qgcm_group_derive_set_keys.argtypes = [vp, u32, u32, u8p, u8p]
+    if hasattr(L, "qgcm_peers_set_keys"):  # (older builds loaded by the A/B tools lack the device ladders)
+        L.qgcm_x25519_batch.argtypes = [u8p, u32, u8p, u32, vp]
+        L.qgcm_x25519_device.argtypes = [vp, u8p, u32, u8p, u32, vp]
+        L.qgcm_peer_keys_device.argtypes = [vp, u8p, u8p, u8p, u8p, u32, vp]
+        L.qgcm_peers_set_keys.argtypes = [vp, u32, u32, u8p, u8p, u8p, u8p]
+        L.qgcm_ecdh_stats.argtypes = [vp, vp, i32]
+        L.qgcm_group_peers_set_keys.argtypes = [vp, u32, u32, u8p, u8p, u8p, u8p]
     L.qgcm_x25519_base.argtypes = [u8p, u8p]
     L.qgcm_x25519.argtypes = [u8p, u8p, u8p]
     L.qgcm_seal_batch.argtypes = [vp, vp, vp, u32, vp, u32, vp, vp]

@@ -112,6 +112,24 @@ class Context:
         _lib.check(_lib.lib().qgcm_derive_set_keys(self.handle, first, n, secrets, salts), "qgcm_derive_set_keys")
         self._reserve(first + n)
 
+    def peers_set_keys(self, first: int, priv_key: bytes, priv_salt: bytes, pub_keys: bytes, pub_salts: bytes) -> None:
+        """common/mapping.go:90-99 for a whole peer table (qgcm_peers_set_keys): key i = PBKDF2(X25519(priv_key,
+        pub_keys[i]), X25519(priv_salt, pub_salts[i])) goes into slot first + i.  From QGCM_KDF_DEVICE_MIN peers
+        on, the ladders and the derivation run on the GPU and no secret, salt or key reaches the host.
+        pub_keys / pub_salts: count * 32 bytes each."""
+        n = _peer_count(priv_key, priv_salt, pub_keys, pub_salts)
+        _lib.check(_lib.lib().qgcm_peers_set_keys(self.handle, first, n, priv_key, priv_salt, pub_keys, pub_salts),
+                   "qgcm_peers_set_keys")
+        self._reserve(first + n)
+
+    def ecdh_stats(self) -> dict:
+        """X25519 ladders run on the device, ladders run on the host by peers_set_keys, ladder kernel launches
+        -- qgcm_ecdh_stats."""
+        names = ("device", "host", "launches")
+        out = (C.c_uint64 * len(names))()
+        n = _lib.check(_lib.lib().qgcm_ecdh_stats(self.handle, out, len(names)), "qgcm_ecdh_stats")
+        return dict(zip(names[:n], (int(x) for x in out)))
+
     def kdf_stats(self) -> dict:
         """Keys derived on the device, keys derived on the host by derive_set_keys, KDF kernel launches,
         install passes (every set_key(s) and derive_set_keys call is one) -- qgcm_kdf_stats."""
@@ -180,6 +198,50 @@ def derive_keys_device(ctx: Context, secrets: bytes, salts: bytes, iters: int = 
     n = _kdf_count(secrets, salts)
     out = C.create_string_buffer(32 * n)
     _lib.check(_lib.lib().qgcm_derive_keys_device(ctx.handle, secrets, salts, n, iters, out), "qgcm_derive_keys_device")
+    return out.raw
+
+
+def _peer_count(priv_key: bytes, priv_salt: bytes, pub_keys: bytes, pub_salts: bytes) -> int:
+    if len(priv_key) != 32 or len(priv_salt) != 32:
+        raise ValueError("the private key and salt must be 32 bytes each")
+    n = len(pub_keys) // 32
+    if len(pub_keys) != 32 * n or len(pub_salts) != 32 * n:
+        raise ValueError("public keys/salts must be count*32 bytes")
+    return n
+
+
+def _ladder_count(scalars: bytes, points: bytes) -> tuple[int, int]:
+    """(count, scalar_stride): one 32-byte scalar for all points, or one per point."""
+    n = len(points) // 32
+    if len(points) != 32 * n or len(scalars) not in (32, 32 * n):
+        raise ValueError("points must be count*32 bytes, scalars 32 or count*32 bytes")
+    return n, 32 if len(scalars) == 32 * n and n != 1 else 0
+
+
+def x25519_batch(scalars: bytes, points: bytes) -> bytes:
+    """GenerateSharedSecret for count points (qgcm_x25519_batch, multithreaded host): out[i] = X25519(scalar i,
+    points[i]).  scalars: 32 bytes (one for all) or count * 32."""
+    n, stride = _ladder_count(scalars, points)
+    out = C.create_string_buffer(32 * n)
+    _lib.check(_lib.lib().qgcm_x25519_batch(scalars, stride, points, n, out), "qgcm_x25519_batch")
+    return out.raw
+
+
+def x25519_device(ctx: Context, scalars: bytes, points: bytes) -> bytes:
+    """x25519_batch on ctx's GPU, one ladder per lane (qgcm_x25519_device): the same bytes."""
+    n, stride = _ladder_count(scalars, points)
+    out = C.create_string_buffer(32 * n)
+    _lib.check(_lib.lib().qgcm_x25519_device(ctx.handle, scalars, stride, points, n, out), "qgcm_x25519_device")
+    return out.raw
+
+
+def peer_keys_device(ctx: Context, priv_key: bytes, priv_salt: bytes, pub_keys: bytes, pub_salts: bytes) -> bytes:
+    """The keys of common/mapping.go:90-99 for count peers, ladders and derivation on ctx's GPU
+    (qgcm_peer_keys_device): key i = PBKDF2(X25519(priv_key, pub_keys[i]), X25519(priv_salt, pub_salts[i]))."""
+    n = _peer_count(priv_key, priv_salt, pub_keys, pub_salts)
+    out = C.create_string_buffer(32 * n)
+    _lib.check(_lib.lib().qgcm_peer_keys_device(ctx.handle, priv_key, priv_salt, pub_keys, pub_salts, n, out),
+               "qgcm_peer_keys_device")
     return out.raw
 
 

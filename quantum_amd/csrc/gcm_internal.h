@@ -256,6 +256,15 @@ hipError_t launch_key_setup(const uint8_t *d_keys, uint32_t first, uint32_t coun
 constexpr uint32_t kKdfLaunchKeys = 1u << 17;
 hipError_t launch_kdf(const uint8_t *d_secrets, const uint8_t *d_salts, uint32_t count, uint32_t iters, uint8_t *d_keys,
                       hipStream_t s, uint32_t *launches);
+// Peer secrets on the device (x25519_kernels.hip, x25519_core.h): d_out[i] = X25519(scalar of lane i,
+// d_points[i]), 32 B each, 4-B aligned, one ladder per lane of x25519_ladder_kernel; d_out may be d_points.
+// scalar_stride 32: lane i's scalar is d_scalars + 32 i; 0: d_scalars for lanes below `split` and d_scalars +
+// 32 from there on (split >= count: one scalar for all).  One launch covers at most kX25519LaunchLanes
+// lanes (the wave slots the kernel's registers leave on 256 CUs: two per SIMD), more go as successive
+// launches on s.  *launches (may be NULL): kernels enqueued.
+constexpr uint32_t kX25519LaunchLanes = 1u << 17;
+hipError_t launch_x25519(const uint8_t *d_scalars, uint32_t scalar_stride, const uint8_t *d_points, uint32_t count,
+                         uint8_t *d_out, uint32_t split, hipStream_t s, uint32_t *launches);
 constexpr uint32_t kKdfDeviceMin = 576;  // qgcm_derive_set_keys derives on the device from this many keys on
                                          // (QGCM_KDF_DEVICE_MIN at qgcm_create; DESIGN.md "Peer keys derived on the GPU")
 // Key slots [first, first + count) take keys src, src + 1, ... of a device key buffer.
@@ -263,12 +272,17 @@ struct KeyRun {
     uint32_t first, count, src;
 };
 // qgcm_api.cpp: one install pass over several runs of slots (qgcm_set_keys is the one-run caller), and
-// derive-then-install for a member's share of a peer table (qgcm_derive_set_keys, group.cpp).  The callers
+// derive-then-install for a member's share of a peer table (qgcm_derive_set_keys, qgcm_peers_set_keys, group.cpp).  The callers
 // check the runs against ctx_max_keys.
 int install_device_keys(qgcm_ctx *ctx, const KeyRun *runs, size_t nruns, uint8_t *d_keys, uint32_t key_count,
                         const uint8_t *h_src);
+// This node's private key and salt and the peers' public ones (32 B each; common/mapping.go:90-92): what
+// derive_install_runs starts from in place of secrets and salts when it is given one (qgcm_peers_set_keys)
+struct PeerPublics {
+    const uint8_t *priv_key, *priv_salt, *pub_keys, *pub_salts;
+};
 int derive_install_runs(qgcm_ctx *ctx, const KeyRun *runs, size_t nruns, uint32_t count, const uint8_t *secrets,
-                        const uint8_t *salts);
+                        const uint8_t *salts, const PeerPublics *pp = nullptr);
 hipError_t launch_fill_uniform(uint8_t *arena, uint64_t stride, uint32_t n, uint32_t len, uint32_t aad_word,
                                uint64_t seed_payload, uint8_t *nonces, uint64_t seed_nonce, hipStream_t s);
 

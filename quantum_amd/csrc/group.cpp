@@ -1024,11 +1024,11 @@ int qgcm_group_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const
     return QGCM_OK;
 }
 
-int qgcm_group_derive_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t *secrets,
-                               const uint8_t *salts) {
-    if (!g || g->m.empty() || (count && (!secrets || !salts))) return QGCM_E_ARG;
-    if ((uint64_t)first_idx + count > g->max_keys) return QGCM_E_KEY;
-    if (count == 0) return QGCM_OK;
+// The body of qgcm_group_derive_set_keys and qgcm_group_peers_set_keys: `secrets` and `salts` are what each
+// peer brings (its secret and salt, or with pp its public key and public salt); pp's private values go to
+// every member.
+static int group_derive_install(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t *secrets,
+                                const uint8_t *salts, const qgcm::PeerPublics *pp) {
     // each member's share: its secrets and salts gathered in index order, and the runs of consecutive
     // slots they fill
     const int G = (int)g->m.size();
@@ -1053,8 +1053,14 @@ int qgcm_group_derive_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count
     for (int k = 0; k < G; ++k) {
         if (!sh[k].count) continue;
         thr.emplace_back([&, k] {
-            rc[k] = qgcm::derive_install_runs(g->m[k].ctx, sh[k].runs.data(), sh[k].runs.size(), sh[k].count,
-                                              sh[k].secrets.data(), sh[k].salts.data());
+            if (pp) {
+                const qgcm::PeerPublics mine{pp->priv_key, pp->priv_salt, sh[k].secrets.data(), sh[k].salts.data()};
+                rc[k] = qgcm::derive_install_runs(g->m[k].ctx, sh[k].runs.data(), sh[k].runs.size(), sh[k].count,
+                                                  nullptr, nullptr, &mine);
+            } else {
+                rc[k] = qgcm::derive_install_runs(g->m[k].ctx, sh[k].runs.data(), sh[k].runs.size(), sh[k].count,
+                                                  sh[k].secrets.data(), sh[k].salts.data());
+            }
         });
     }
     for (auto &t : thr) t.join();
@@ -1065,6 +1071,23 @@ int qgcm_group_derive_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count
     for (int k = 0; k < G; ++k)
         if (rc[k] != QGCM_OK) return rc[k];  // the first error; members that finished keep their keys
     return QGCM_OK;
+}
+
+int qgcm_group_derive_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t *secrets,
+                               const uint8_t *salts) {
+    if (!g || g->m.empty() || (count && (!secrets || !salts))) return QGCM_E_ARG;
+    if ((uint64_t)first_idx + count > g->max_keys) return QGCM_E_KEY;
+    if (count == 0) return QGCM_OK;
+    return group_derive_install(g, first_idx, count, secrets, salts, nullptr);
+}
+
+int qgcm_group_peers_set_keys(qgcm_group *g, uint32_t first_idx, uint32_t count, const uint8_t priv_key[32],
+                              const uint8_t priv_salt[32], const uint8_t *pub_keys, const uint8_t *pub_salts) {
+    if (!g || g->m.empty() || !priv_key || !priv_salt || (count && (!pub_keys || !pub_salts))) return QGCM_E_ARG;
+    if ((uint64_t)first_idx + count > g->max_keys) return QGCM_E_KEY;
+    if (count == 0) return QGCM_OK;
+    const qgcm::PeerPublics pp{priv_key, priv_salt, pub_keys, pub_salts};
+    return group_derive_install(g, first_idx, count, pub_keys, pub_salts, &pp);
 }
 
 int qgcm_group_clear_keys(qgcm_group *g, uint32_t first_idx, uint32_t count) {

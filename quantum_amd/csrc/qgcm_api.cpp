@@ -170,6 +170,9 @@ struct qgcm_ctx {
     // keys derived on the device, keys derived on the host by qgcm_derive_set_keys, KDF kernel launches,
     // install passes (qgcm_kdf_stats)
     std::atomic<uint64_t> kdf_stats[4] = {};
+    // X25519 ladders run on the device, ladders run on the host by qgcm_peers_set_keys, ladder kernel
+    // launches (qgcm_ecdh_stats); the device ladders share the derivation stream and kdf_mu
+    std::atomic<uint64_t> ecdh_stats[3] = {};
 };
 
 namespace {
@@ -727,27 +730,46 @@ int qgcm::install_device_keys(qgcm_ctx *ctx, const KeyRun *runs, size_t nruns, u
 
 namespace {
 
-// d_keys[i] = PBKDF2(secrets[i], salts[i], iters) for host arrays, on the context's derivation stream;
-// complete on return.  h_out (may be NULL): the keys copied to host memory, and d_keys zeroed behind the
-// copy.  Holds kdf_mu only.
-int kdf_on_device(qgcm_ctx *ctx, const uint8_t *secrets, const uint8_t *salts, uint32_t count, uint32_t iters,
-                  uint8_t *d_keys, uint8_t *h_out) {
-    std::lock_guard<std::mutex> lk(ctx->kdf_mu);
-    if (!ctx->kdf_stream && hipStreamCreateWithFlags(&ctx->kdf_stream, hipStreamNonBlocking) != hipSuccess) {
+// the context's derivation stream, created by the first caller (kdf_mu held); NULL: no stream
+hipStream_t kdf_stream_locked(qgcm_ctx *ctx) {
+    if (!ctx->kdf_stream && hipStreamCreateWithFlags(&ctx->kdf_stream, hipStreamNonBlocking) != hipSuccess)
         ctx->kdf_stream = nullptr;
-        return QGCM_E_HIP;
-    }
-    hipStream_t s = ctx->kdf_stream;
+    return ctx->kdf_stream;
+}
+
+// d_keys[i] = PBKDF2(secrets[i], salts[i], iters) for host arrays, on the context's derivation stream;
+// complete on return.  With pp the secrets and salts are not given but computed on the device first
+// (common/mapping.go:90-92): pp's public values take their place in the input buffer, and one ladder launch
+// over 2 * count lanes turns them, in place, into secrets[i] = X25519(priv_key, pub_keys[i]) and salts[i] =
+// X25519(priv_salt, pub_salts[i]); the derivation follows on the same stream.  h_out (may be NULL): the keys
+// copied to host memory, and d_keys zeroed behind the copy.  Holds kdf_mu only.
+int kdf_on_device(qgcm_ctx *ctx, const uint8_t *secrets, const uint8_t *salts, uint32_t count, uint32_t iters,
+                  uint8_t *d_keys, uint8_t *h_out, const PeerPublics *pp = nullptr) {
+    if (pp && count > 0x7fffffffu) return QGCM_E_ARG;  // 2 * count lanes
+    std::lock_guard<std::mutex> lk(ctx->kdf_mu);
+    hipStream_t s = kdf_stream_locked(ctx);
+    if (!s) return QGCM_E_HIP;
     const size_t bytes = (size_t)count * 32;
-    uint8_t *d_in = nullptr;  // secrets, then salts
-    if (hipMalloc(&d_in, 2 * bytes) != hipSuccess) return QGCM_E_NOMEM;
-    uint32_t launches = 0;
+    uint8_t *d_in = nullptr;  // secrets, then salts, then (pp) the two private scalars
+    const size_t in_bytes = 2 * bytes + (pp ? 64 : 0);
+    if (hipMalloc(&d_in, in_bytes) != hipSuccess) return QGCM_E_NOMEM;
+    uint32_t launches = 0, ladder_launches = 0;
     int rc = QGCM_OK;
+    if (pp) {
+        secrets = pp->pub_keys;
+        salts = pp->pub_salts;
+    }
     if (hipMemcpyAsync(d_in, secrets, bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(d_in + bytes, salts, bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
-        launch_kdf(d_in, d_in + bytes, count, iters, d_keys, s, &launches) != hipSuccess)
+        hipMemcpyAsync(d_in + bytes, salts, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
         rc = QGCM_E_HIP;
-    if (hipMemsetAsync(d_in, 0, 2 * bytes, s) != hipSuccess) rc = QGCM_E_HIP;  // the secrets do not outlive the call
+    if (rc == QGCM_OK && pp &&
+        (hipMemcpyAsync(d_in + 2 * bytes, pp->priv_key, 32, hipMemcpyHostToDevice, s) != hipSuccess ||
+         hipMemcpyAsync(d_in + 2 * bytes + 32, pp->priv_salt, 32, hipMemcpyHostToDevice, s) != hipSuccess ||
+         launch_x25519(d_in + 2 * bytes, 0, d_in, 2 * count, d_in, count, s, &ladder_launches) != hipSuccess))
+        rc = QGCM_E_HIP;
+    if (rc == QGCM_OK && launch_kdf(d_in, d_in + bytes, count, iters, d_keys, s, &launches) != hipSuccess) rc = QGCM_E_HIP;
+    // the secrets (and private scalars) do not outlive the call
+    if (hipMemsetAsync(d_in, 0, in_bytes, s) != hipSuccess) rc = QGCM_E_HIP;
     if (h_out) {
         if (rc == QGCM_OK && hipMemcpyAsync(h_out, d_keys, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) rc = QGCM_E_HIP;
         if (hipMemsetAsync(d_keys, 0, bytes, s) != hipSuccess) rc = QGCM_E_HIP;
@@ -755,7 +777,11 @@ int kdf_on_device(qgcm_ctx *ctx, const uint8_t *secrets, const uint8_t *salts, u
     if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
     hipFree(d_in);
     ctx->kdf_stats[2].fetch_add(launches, std::memory_order_relaxed);
-    if (rc == QGCM_OK) ctx->kdf_stats[0].fetch_add(count, std::memory_order_relaxed);
+    ctx->ecdh_stats[2].fetch_add(ladder_launches, std::memory_order_relaxed);
+    if (rc == QGCM_OK) {
+        ctx->kdf_stats[0].fetch_add(count, std::memory_order_relaxed);
+        if (pp) ctx->ecdh_stats[0].fetch_add(2ull * count, std::memory_order_relaxed);
+    }
     return rc;
 }
 
@@ -768,22 +794,34 @@ void wipe_device_keys(qgcm_ctx *ctx, uint8_t *d_keys, uint32_t count) {
 
 }  // namespace
 
-// NewAES for `count` peers whose slots are the runs (their src fields index secrets / salts): derive on
-// the device at or above the context's threshold, else on the host, then one install pass.
+// NewAES for `count` peers whose slots are the runs (their src fields index secrets / salts, or pp's public
+// values): derive on the device at or above the context's threshold, else on the host, then one install
+// pass.  With pp (secrets and salts NULL) the secrets and salts are X25519 outputs, computed where the keys
+// are derived: by the ladder kernel in front of the derivation, or by qgcm_x25519_batch on the host.
 int qgcm::derive_install_runs(qgcm_ctx *ctx, const KeyRun *runs, size_t nruns, uint32_t count, const uint8_t *secrets,
-                              const uint8_t *salts) {
+                              const uint8_t *salts, const PeerPublics *pp) {
     if (count == 0) return QGCM_OK;
     if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
     uint8_t *d_keys = nullptr;
     if (hipMalloc(&d_keys, (size_t)count * 32) != hipSuccess) return QGCM_E_NOMEM;
     int rc;
     if (ctx->kdf_device_min && count >= ctx->kdf_device_min) {
-        rc = kdf_on_device(ctx, secrets, salts, count, QGCM_PBKDF2_ITERS, d_keys, nullptr);
+        rc = kdf_on_device(ctx, secrets, salts, count, QGCM_PBKDF2_ITERS, d_keys, nullptr, pp);
         if (rc == QGCM_OK) rc = install_device_keys(ctx, runs, nruns, d_keys, count, nullptr);
         else wipe_device_keys(ctx, d_keys, count);
     } else {
-        std::vector<uint8_t> keys((size_t)count * 32);
-        rc = qgcm_derive_keys(secrets, salts, count, keys.data());
+        std::vector<uint8_t> keys((size_t)count * 32), shared;
+        rc = QGCM_OK;
+        if (pp) {
+            shared.resize((size_t)count * 64);  // secrets, then salts
+            rc = qgcm_x25519_batch(pp->priv_key, 0, pp->pub_keys, count, shared.data());
+            if (rc == QGCM_OK) rc = qgcm_x25519_batch(pp->priv_salt, 0, pp->pub_salts, count, shared.data() + (size_t)count * 32);
+            if (rc == QGCM_OK) ctx->ecdh_stats[1].fetch_add(2ull * count, std::memory_order_relaxed);
+            secrets = shared.data();
+            salts = shared.data() + (size_t)count * 32;
+        }
+        if (rc == QGCM_OK) rc = qgcm_derive_keys(secrets, salts, count, keys.data());
+        if (!shared.empty()) explicit_bzero(shared.data(), shared.size());
         if (rc == QGCM_OK) {
             ctx->kdf_stats[1].fetch_add(count, std::memory_order_relaxed);
             rc = install_device_keys(ctx, runs, nruns, d_keys, count, keys.data());
@@ -1018,6 +1056,91 @@ int qgcm_derive_set_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, cons
     if (count == 0) return QGCM_OK;
     const KeyRun run{first_idx, count, 0};
     return derive_install_runs(ctx, &run, 1, count, secrets, salts);
+}
+
+int qgcm_x25519_batch(const uint8_t *scalars, uint32_t scalar_stride, const uint8_t *points, uint32_t count,
+                      uint8_t *out) {
+    if (count && (!scalars || !points || !out)) return QGCM_E_ARG;
+    if (scalar_stride != 0 && scalar_stride != 32) return QGCM_E_ARG;
+    if (!count) return QGCM_OK;
+    unsigned nt = std::thread::hardware_concurrency();
+    if (nt == 0) nt = 1;
+    if (nt > 64) nt = 64;
+    if (nt > count) nt = count;
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; ++t)
+        th.emplace_back([=] {
+            for (uint32_t i = t; i < count; i += nt)
+                qgcm_x25519(out + 32ull * i, scalars + (uint64_t)scalar_stride * i, points + 32ull * i);
+        });
+    for (auto &x : th) x.join();
+    return QGCM_OK;
+}
+
+int qgcm_x25519_device(qgcm_ctx *ctx, const uint8_t *scalars, uint32_t scalar_stride, const uint8_t *points,
+                       uint32_t count, uint8_t *out) {
+    if (!ctx || (count && (!scalars || !points || !out))) return QGCM_E_ARG;
+    if (scalar_stride != 0 && scalar_stride != 32) return QGCM_E_ARG;
+    if (count == 0) return QGCM_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    std::lock_guard<std::mutex> lk(ctx->kdf_mu);
+    hipStream_t s = kdf_stream_locked(ctx);
+    if (!s) return QGCM_E_HIP;
+    const size_t bytes = (size_t)count * 32, kbytes = scalar_stride ? bytes : 32;
+    uint8_t *d = nullptr;  // points (the outputs take their place), then the scalars
+    if (hipMalloc(&d, bytes + kbytes) != hipSuccess) return QGCM_E_NOMEM;
+    // into a bounce buffer, so that a failed call leaves `out` untouched
+    std::vector<uint8_t> res(bytes);
+    uint32_t launches = 0;
+    int rc = QGCM_OK;
+    if (hipMemcpyAsync(d, points, bytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d + bytes, scalars, kbytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_x25519(d + bytes, scalar_stride, d, count, d, count, s, &launches) != hipSuccess ||
+        hipMemcpyAsync(res.data(), d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess)
+        rc = QGCM_E_HIP;
+    if (hipMemsetAsync(d, 0, bytes + kbytes, s) != hipSuccess) rc = QGCM_E_HIP;  // scalars and secrets end with the call
+    if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
+    hipFree(d);
+    ctx->ecdh_stats[2].fetch_add(launches, std::memory_order_relaxed);
+    if (rc == QGCM_OK) {
+        ctx->ecdh_stats[0].fetch_add(count, std::memory_order_relaxed);
+        memcpy(out, res.data(), bytes);
+    }
+    explicit_bzero(res.data(), res.size());
+    return rc;
+}
+
+int qgcm_peer_keys_device(qgcm_ctx *ctx, const uint8_t priv_key[32], const uint8_t priv_salt[32],
+                          const uint8_t *pub_keys, const uint8_t *pub_salts, uint32_t count, uint8_t *keys) {
+    if (!ctx || !priv_key || !priv_salt || (count && (!pub_keys || !pub_salts || !keys))) return QGCM_E_ARG;
+    if (count == 0) return QGCM_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    uint8_t *d_keys = nullptr;
+    if (hipMalloc(&d_keys, (size_t)count * 32) != hipSuccess) return QGCM_E_NOMEM;
+    std::vector<uint8_t> out((size_t)count * 32);
+    const PeerPublics pp{priv_key, priv_salt, pub_keys, pub_salts};
+    const int rc = kdf_on_device(ctx, nullptr, nullptr, count, QGCM_PBKDF2_ITERS, d_keys, out.data(), &pp);
+    hipFree(d_keys);
+    if (rc == QGCM_OK) memcpy(keys, out.data(), out.size());
+    explicit_bzero(out.data(), out.size());
+    return rc;
+}
+
+int qgcm_peers_set_keys(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, const uint8_t priv_key[32],
+                        const uint8_t priv_salt[32], const uint8_t *pub_keys, const uint8_t *pub_salts) {
+    if (!ctx || !priv_key || !priv_salt || (count && (!pub_keys || !pub_salts))) return QGCM_E_ARG;
+    if ((uint64_t)first_idx + count > ctx->max_keys) return QGCM_E_KEY;
+    if (count == 0) return QGCM_OK;
+    const KeyRun run{first_idx, count, 0};
+    const PeerPublics pp{priv_key, priv_salt, pub_keys, pub_salts};
+    return derive_install_runs(ctx, &run, 1, count, nullptr, nullptr, &pp);
+}
+
+int qgcm_ecdh_stats(const qgcm_ctx *ctx, uint64_t *out, int n) {
+    if (!ctx || !out || n < 0) return -1;
+    const int m = std::min(n, 3);
+    for (int i = 0; i < m; ++i) out[i] = ctx->ecdh_stats[i].load(std::memory_order_relaxed);
+    return m;
 }
 
 int qgcm_kdf_stats(const qgcm_ctx *ctx, uint64_t *out, int n) {

@@ -157,6 +157,18 @@ class Group:
         _lib.check(_lib.lib().qgcm_group_derive_set_keys(self.handle, first, n, secrets, salts),
                    "qgcm_group_derive_set_keys")
 
+    def peers_set_keys(self, first: int, priv_key: bytes, priv_salt: bytes, pub_keys: bytes, pub_salts: bytes) -> None:
+        """qgcm_group_peers_set_keys: key i = PBKDF2(X25519(priv_key, pub_keys[i]), X25519(priv_salt,
+        pub_salts[i])) into slot first + i of its owning member; the members run their shares' ladders and
+        derivations at once and install them in one pass each."""
+        from . import _lib
+
+        n = len(pub_keys) // 32
+        if len(priv_key) != 32 or len(priv_salt) != 32 or len(pub_keys) != 32 * n or len(pub_salts) != 32 * n:
+            raise ValueError("private key/salt must be 32 bytes, public keys/salts count*32 bytes")
+        _lib.check(_lib.lib().qgcm_group_peers_set_keys(self.handle, first, n, priv_key, priv_salt, pub_keys, pub_salts),
+                   "qgcm_group_peers_set_keys")
+
     def _run(self, seal: bool, arena_ptr: int, descs, n: int, nonces_ptr, aad_len: int, status_ptr) -> int:
         from . import _lib
 
