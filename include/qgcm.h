@@ -13,6 +13,11 @@
  *   plugin/encryption.go:16-40 Encryption.Apply calls Encrypt/Decrypt per packet (qgcm_seal_one /
  *                         qgcm_open_one); workers that batch their packets call the host or device
  *                         batch entry points instead.
+ *   worker/outgoing.go:28-35, worker/incoming.go:28-34 resolve -> router/router.go:21-31 Resolve
+ *                         -> qgcm_routes_set + qgcm_resolve_outgoing / qgcm_resolve_incoming
+ *   worker/outgoing.go:37-53 stats, metric/aggregator.go:24-68 -> qgcm_route_account / qgcm_route_stats
+ *   Outgoing.pipeline / Incoming.pipeline for a batch         -> qgcm_route_seal_host / qgcm_route_open_host
+ *   socket/udp.go:44-47 Write(payload, mapping)               -> qgcm_udp_send_slots_to
  *
  * Error convention follows the reference's own cgo layer (crypto/dtls.go:37-40, dtls.h:43-48):
  * constructors return NULL and fill a caller-supplied error buffer; everything else returns
@@ -434,6 +439,92 @@ int qgcm_tun_up(const char *ifname, const char *ip, int prefix, int mtu);
 int qgcm_tun_read_slots(int fd, uint8_t *arena, uint64_t stride, uint32_t max_n, uint32_t *lens, int timeout_ms);
 int qgcm_tun_write_slots(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens);
 int qgcm_tun_close(int fd);
+
+/* ---- routes resolved on the GPU (worker resolve + stats) ---- */
+/* The route table: the datastore's private-IP -> mapping map (etcdv2.go:210-234 sync) with the peer's key
+ * slot in place of the Mapping, plus the values router/router.go:21-31 resolves with.  Addresses are
+ * common.IPtoInt values (common/common.go:42-45): the little-endian uint32 of the four address bytes, so
+ * 10.99.0.1 is 0x0100630a.  net / mask: cfg.NetworkConfig.IPNet; gateway: the datastore's gateway address
+ * (etcdv2.go:285-288); own_ip: cfg.PrivateIP.
+ *
+ * qgcm_routes_set replaces the whole table (count 0: an empty one).  A duplicate ip takes its last entry,
+ * as a map assignment does.  A peer at or above the context's max_keys: QGCM_E_ARG, nothing installed.
+ * Before the first qgcm_routes_set every qgcm_resolve_*, qgcm_route_* call returns QGCM_E_ARG.  The table
+ * is built on the host (open addressing, linear probing, a power-of-two capacity of at least 2 * count,
+ * 8-byte entries {ip, peer}, peer QGCM_NO_PEER = empty), uploaded into a fresh allocation, and the
+ * context's pointer is swapped under the context's route lock.  A launch takes pointer and capacity as
+ * kernel arguments: a resolve enqueued before qgcm_routes_set returns sees the old table whole, one
+ * enqueued after it the new one whole.  The old table is released with hipFree after the swap, which waits
+ * for the device -- so for the launches that use it; qgcm_routes_set is a control-plane call and may take
+ * that long.  Keys are not touched: a route may name a slot whose key is not set (its packets then
+ * resolve, and the seal rejects them with status 0). */
+#define QGCM_NO_PEER 0xffffffffu
+typedef struct qgcm_route { uint32_t ip; uint32_t peer; } qgcm_route;
+typedef struct qgcm_route_net { uint32_t net, mask, gateway, own_ip; } qgcm_route_net;
+int qgcm_routes_set(qgcm_ctx *ctx, const qgcm_route *routes, uint32_t count, const qgcm_route_net *net);
+/* One launch turns a batch of raw slots into peer indices and seal / open descriptors.  Slot i at i * stride
+ * in device memory (4-B aligned; stride a nonzero multiple of 4), d_lens / d_peer n uint32 each, d_descs n
+ * descriptors (16-B aligned); n at most QGCM_MAX_BATCH, n == 0: QGCM_OK, nothing launched.  Bad
+ * arguments: QGCM_E_ARG.  Asynchronous on stream.
+ *
+ * outgoing: d_lens[i] is the TUN packet length (qgcm_tun_read_slots), the packet at slot + 4.  The
+ * destination is Packet[16:20] (no IP-version check, as outgoing.go:29 makes none); inside the net
+ * ((dst & mask) == (net & mask)) it is looked up itself, else the gateway is (router.go:25-30).  Hit: own_ip
+ * into Raw[0:4] (outgoing.go:30), d_peer[i] = peer, d_descs[i] = {i * stride, d_lens[i], peer}.  Miss:
+ * d_peer[i] = QGCM_NO_PEER, d_descs[i] = {i * stride, d_lens[i], QGCM_NO_PEER}, the slot untouched byte
+ * for byte -- qgcm_seal_batch rejects that key index with status 0 and leaves the slot alone too.
+ * incoming: d_lens[i] is the datagram length (qgcm_udp_recv_slots, Raw[:n]); the sender is Raw[0:4], the
+ * rule the same (incoming.go:29); d_descs[i] = {i * stride, d_lens[i] - 4, peer or QGCM_NO_PEER}; the arena
+ * is only read.
+ * Divergences, all treated as a miss: an outgoing packet shorter than 20 bytes (the reference slices
+ * stale buffer bytes there); an outgoing packet with 4 + len + 28 > stride (the reference's MTU rules it
+ * out); an incoming datagram shorter than 4 bytes (descriptor length 0) or longer than stride. */
+int qgcm_resolve_outgoing(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+                          uint32_t *d_peer, qgcm_desc *d_descs, void *stream);
+int qgcm_resolve_incoming(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+                          uint32_t *d_peer, qgcm_desc *d_descs, void *stream);
+/* Link metrics (metric.Metrics, metric/aggregator.go:24-32): per direction the context holds four uint64
+ * counters {Packets, Bytes, DroppedPackets, DroppedBytes} for the totals and four per key slot for the
+ * links, in device memory, zero at the first qgcm_routes_set.  qgcm_route_account adds one batch, after its
+ * seal (QGCM_TX) or open (QGCM_RX) on the same stream: d_descs are the descriptors that call took, d_status
+ * its status array (NULL: every resolved packet was delivered).  With len = d_descs[i].len:
+ *   d_peer[i] == QGCM_NO_PEER:  totals DroppedPackets += 1, bytes 0 (resolve returned nil: outgoing.go:34,
+ *                               incoming.go:33, stats at :44-50); no link
+ *   delivered, Tx:              totals and link  Packets += 1, Bytes += 4 + len + 28 (encryption.go:36-37)
+ *   delivered, Rx:              totals and link  Packets += 1, Bytes += 4 + len - 28
+ *   resolved but status 0:      totals and link  DroppedPackets += 1, DroppedBytes += 4 + len (Apply
+ *                               returned its inputs: the length the packet came with)
+ * An Rx packet with len < 28 counts as dropped whatever its status (the open rejects it); a d_peer[i] at or
+ * above max_keys counts as unresolved.  The sums are exact integers, added with 64-bit atomics after the
+ * packets of a wave and of a workgroup that share a link were summed on chip, so calls on several streams
+ * may run at once.  Per-queue counters are the caller's to keep: a batch comes from one queue, so the
+ * batch's own sums are that queue's.
+ * qgcm_route_stats copies one set of four out (peer QGCM_NO_PEER: the totals; a peer at or above max_keys:
+ * QGCM_E_ARG).  It reports what completed accounting launches have added: synchronise the streams first. */
+#define QGCM_TX 0
+#define QGCM_RX 1
+int qgcm_route_account(qgcm_ctx *ctx, int dir, uint32_t n, const uint32_t *d_peer, const qgcm_desc *d_descs,
+                       const uint8_t *d_status, void *stream);
+int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]);
+/* Outgoing.pipeline / Incoming.pipeline for a batch in host memory (pinned or pageable), slot i at
+ * i * stride: in chunks of at most 65536 packets, on one stream of the context: copy in, resolve, seal or
+ * open (aad_len 4, the semantics of qgcm_seal_batch / qgcm_open_batch), account as Tx / Rx, copy back.
+ * Synchronous; one call at a time per context (calls are serialized); the chunks are not pipelined.
+ * seal: h_lens[i] in: the TUN packet length L; out: the datagram length 4 + L + 28, or 0 for a dropped
+ * packet.  h_nonces as in qgcm_seal_host: n * 12 bytes, NULL (the nonce is in the slot) or
+ * QGCM_NONCES_GENERATE.  open: h_lens[i] in: the datagram length; out: the plaintext packet length (what
+ * qgcm_tun_write_slots takes), or 0.  Both: h_peer[i] = the peer or QGCM_NO_PEER; h_status[i] (may be NULL)
+ * 1 or 0; returns the number of dropped packets or a negative error. */
+int qgcm_route_seal_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                         const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status);
+int qgcm_route_open_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                         uint32_t *h_peer, uint8_t *h_status);
+/* socket/udp.go:44-47 with mapping.Sockaddr per packet: datagram i (Raw[:lens[i]] of slot i) goes to
+ * addrs[peer[i]], in sendmmsg batches.  Packets with peer[i] == QGCM_NO_PEER or lens[i] == 0 are skipped.
+ * Returns the number sent, or -1 (also, before anything is sent, when some peer[i] >= n_addrs). */
+typedef struct qgcm_peer_addr { uint32_t ip; uint16_t port; uint16_t pad; } qgcm_peer_addr; /* network byte order */
+int qgcm_udp_send_slots_to(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
+                           const uint32_t *peer, const qgcm_peer_addr *addrs, uint32_t n_addrs);
 
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19

@@ -8,15 +8,16 @@ Layout:
   quantum_amd/common.py     common.Payload and constants mirror (common/payload.go, common.go)
   quantum_amd/batch.py      device-resident batch entry points (throughput path)
   quantum_amd/worker.py     worker.Outgoing / Incoming pipeline mirror (worker/outgoing.go, incoming.go)
+  quantum_amd/route.py      router.Router mirror (router/router.go) and the batched route / metrics calls
 """
 from . import common, plugin, worker  # noqa: F401
 from ._lib import QgcmError, lib  # noqa: F401
 
-__all__ = ["common", "plugin", "worker", "crypto", "batch", "lib", "QgcmError"]
+__all__ = ["common", "plugin", "worker", "crypto", "batch", "route", "lib", "QgcmError"]
 
 
 def __getattr__(name):
-    if name in ("crypto", "batch"):
+    if name in ("crypto", "batch", "route"):
         import importlib
 
         return importlib.import_module(f".{name}", __name__)

@@ -37,6 +37,8 @@ EXPORTS = (
     "qgcm_group_create", "qgcm_group_destroy", "qgcm_group_size", "qgcm_group_ctx", "qgcm_group_shard",
     "qgcm_group_set_keys", "qgcm_group_clear_keys", "qgcm_group_seal_host", "qgcm_group_open_host", "qgcm_group_member_cpus",
     "qgcm_group_last_zerocopy", "qgcm_group_last_path", "qgcm_group_order", "qgcm_launch_counts", "qgcm_resident_stop", "qgcm_resident_stats",
+    "qgcm_routes_set", "qgcm_resolve_outgoing", "qgcm_resolve_incoming", "qgcm_route_account", "qgcm_route_stats",
+    "qgcm_route_seal_host", "qgcm_route_open_host", "qgcm_udp_send_slots_to",
 )
 
 QGCM_OK = 0
@@ -46,6 +48,8 @@ QGCM_E_KEY = -3
 QGCM_E_AUTH = -4
 QGCM_E_NOMEM = -5
 OVERHEAD = 28
+NO_PEER = 0xFFFFFFFF  # QGCM_NO_PEER: a packet no route resolves, an empty route-table entry
+TX, RX = 0, 1  # QGCM_TX / QGCM_RX
 QGCM_MAX_AAD = 16384  # longest additional data of a per-packet call (qgcm_seal_one / qgcm_open_one)
 ERRLEN = 120
 # QGCM_NONCES_GENERATE: as the nonce argument of a batch seal, "draw the nonces on the GPU from the
@@ -61,6 +65,24 @@ class Desc(C.Structure):
     """qgcm_desc: {offset u64, len u32, key_idx u32} -- 16 bytes."""
 
     _fields_ = [("offset", C.c_uint64), ("len", C.c_uint32), ("key_idx", C.c_uint32)]
+
+
+class Route(C.Structure):
+    """qgcm_route: {ip u32 (common.IPtoInt), peer u32 (key slot)}."""
+
+    _fields_ = [("ip", C.c_uint32), ("peer", C.c_uint32)]
+
+
+class RouteNet(C.Structure):
+    """qgcm_route_net: {net, mask, gateway, own_ip}, all common.IPtoInt values."""
+
+    _fields_ = [("net", C.c_uint32), ("mask", C.c_uint32), ("gateway", C.c_uint32), ("own_ip", C.c_uint32)]
+
+
+class PeerAddr(C.Structure):
+    """qgcm_peer_addr: {ip u32, port u16, pad u16}, network byte order."""
+
+    _fields_ = [("ip", C.c_uint32), ("port", C.c_uint16), ("pad", C.c_uint16)]
 
 
 _lib: C.CDLL | None = None
@@ -166,6 +188,15 @@ def _bind(L: C.CDLL) -> None:
         if hasattr(L, "qgcm_group_last_path"):
             L.qgcm_group_last_path.argtypes = [vp, i32]
             L.qgcm_group_order.argtypes = [vp, vp, u32, vp, vp]
+    if hasattr(L, "qgcm_routes_set"):  # (older builds loaded by the A/B tools lack the router)
+        L.qgcm_routes_set.argtypes = [vp, vp, u32, vp]
+        L.qgcm_resolve_outgoing.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp]
+        L.qgcm_resolve_incoming.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp]
+        L.qgcm_route_account.argtypes = [vp, i32, u32, vp, vp, vp, vp]
+        L.qgcm_route_stats.argtypes = [vp, i32, u32, vp]
+        L.qgcm_route_seal_host.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp]
+        L.qgcm_route_open_host.argtypes = [vp, vp, u64, u32, vp, vp, vp]
+        L.qgcm_udp_send_slots_to.argtypes = [C.c_int, vp, u64, u32, vp, vp, vp, u32]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

@@ -308,4 +308,43 @@ enum NonceDest { kNonceArray = 0, kNonceUniform = 1, kNonceDescs = 2 };
 // gets no nonce -- its slot stays untouched -- but keeps its stream position.
 hipError_t launch_nonce_fill(NonceDest dest, const NonceArgs &a, int num_cus, hipStream_t s);
 
+// Routes and link metrics (route.cpp, route_kernels.hip; include/qgcm.h "routes resolved on the GPU").
+// The table: `cap_mask + 1` entries {ip, peer} (a power of two, at least twice the routes), entry of ip
+// at route_hash(ip) & cap_mask or the next free one (linear probing), peer == QGCM_NO_PEER = empty.  The
+// host builds it and the kernel probes it with the same hash.
+inline __host__ __device__ uint32_t route_hash(uint32_t ip) {
+    uint32_t h = ip * 0x9E3779B1u;  // addresses of one subnet differ in their last byte: the top bits of ip
+    return h ^ (h >> 15);
+}
+struct RouteArgs {
+    const uint2 *table;
+    uint32_t cap_mask;
+    uint32_t net, mask, gateway, own_ip;  // common.IPtoInt convention
+    uint8_t *arena;                       // 4-B aligned; incoming: read only
+    uint64_t stride;                      // a multiple of 4
+    uint32_t n;
+    const uint32_t *lens;
+    uint32_t *peer;
+    qgcm_desc *descs;                     // 16-B aligned
+};
+hipError_t launch_route_resolve(bool outgoing, const RouteArgs &a, hipStream_t s);
+struct RouteAccountArgs {
+    unsigned long long *counters;  // one direction: [0, 4) the totals, [4 + 4 p, 8 + 4 p) link p
+    uint32_t max_keys;
+    int dir;                       // QGCM_TX / QGCM_RX
+    uint32_t n;
+    const uint32_t *peer;
+    const qgcm_desc *descs;
+    const uint8_t *status;         // NULL: every resolved packet was delivered
+};
+hipError_t launch_route_account(const RouteAccountArgs &a, int num_cus, hipStream_t s);
+// The context's route state (route.cpp): made by qgcm_create, freed by qgcm_destroy after the device is idle.
+struct RouteState;
+RouteState *route_state_create();
+void route_state_destroy(RouteState *r);
+RouteState *ctx_route(qgcm_ctx *ctx);
+uint32_t ctx_max_keys(const qgcm_ctx *ctx);
+int ctx_device(const qgcm_ctx *ctx);
+int ctx_num_cus(const qgcm_ctx *ctx);
+
 }  // namespace qgcm

@@ -173,6 +173,9 @@ struct qgcm_ctx {
     // X25519 ladders run on the device, ladders run on the host by qgcm_peers_set_keys, ladder kernel
     // launches (qgcm_ecdh_stats); the device ladders share the derivation stream and kdf_mu
     std::atomic<uint64_t> ecdh_stats[3] = {};
+
+    // the route table, link counters and host-pipeline staging of the qgcm_route* calls (route.cpp)
+    qgcm::RouteState *route = nullptr;
 };
 
 namespace {
@@ -349,6 +352,10 @@ bool key_ok(qgcm_ctx *ctx, uint32_t k) {
 bool qgcm::ctx_one_kernel(const qgcm_ctx *ctx) { return ctx->one_kernel; }
 hipStream_t qgcm::ctx_pipe(qgcm_ctx *ctx, int k) { return ctx->pipe[k]; }
 std::mutex &qgcm::ctx_io_mu(qgcm_ctx *ctx) { return ctx->io_mu; }
+qgcm::RouteState *qgcm::ctx_route(qgcm_ctx *ctx) { return ctx->route; }
+uint32_t qgcm::ctx_max_keys(const qgcm_ctx *ctx) { return ctx->max_keys; }
+int qgcm::ctx_device(const qgcm_ctx *ctx) { return ctx->device; }
+int qgcm::ctx_num_cus(const qgcm_ctx *ctx) { return ctx->num_cus; }
 
 uint32_t qgcm::descs_one_max(const qgcm_ctx *ctx) {
     return ctx->one_kernel && !ctx->variant_forced && ctx->desc_one_on ? ctx->desc_one_max : 0u;
@@ -898,6 +905,7 @@ qgcm_ctx *qgcm_create(int device, uint32_t max_keys, char *err, int errlen) {
     ctx->num_cus = prop.multiProcessorCount;
     ctx->max_keys = max_keys;
     ctx->key_set.assign(max_keys, 0);
+    ctx->route = route_state_create();
     if (const char *v = getenv("QGCM_VARIANT")) {  // kernel variant overrides (tuning and tests)
         const int iv = atoi(v);
         if (variant_valid(iv) && !variant_desc(iv)) {
@@ -992,6 +1000,7 @@ void qgcm_destroy(qgcm_ctx *ctx) {
     hipFree(ctx->d_sbox);
     hipFree(ctx->d_key_valid);
     hipFree(ctx->d_qws);
+    route_state_destroy(ctx->route);
     auto free_slot = [](qgcm_ctx::OneSlot &sl) {
         if (sl.h) hipHostFree(sl.h);
         if (sl.stream) hipStreamDestroy(sl.stream);

@@ -1,0 +1,273 @@
+// route.cpp -- the route table, the link counters and the routed host pipelines of include/qgcm.h
+// ("routes resolved on the GPU").  Host work only: the open-addressing table is built here
+// and uploaded, the kernels of route_kernels.hip do everything per packet.
+//
+// Table lifetime: qgcm_routes_set uploads the new table into a fresh allocation, swaps the context's
+// pointer under the route lock, and then releases the old allocation with hipFree, which waits for the
+// device: every launch that took the old pointer as its argument has finished by then.  A resolve holds
+// the route lock from reading the pointer until its kernel is enqueued, so it never launches with a table
+// that is already freed.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "../../include/qgcm.h"
+#include "gcm_internal.h"
+
+namespace qgcm {
+
+constexpr uint32_t kRouteChunk = 65536;         // packets per chunk of the routed host pipelines
+constexpr uint64_t kRouteChunkBytes = 256ull << 20;  // ... and bytes of slots
+
+struct RouteState {
+    std::mutex mu;  // the table pointer, the net and the counters' allocation
+    bool set = false;
+    uint2 *d_table = nullptr;
+    uint32_t cap_mask = 0;
+    qgcm_route_net net{};
+    unsigned long long *d_counters = nullptr;  // [2 directions][1 + max_keys][4]
+    size_t dir_words = 0;                      // 4 * (1 + max_keys)
+
+    // the routed host pipelines: one stream, device staging grown on demand, one call at a time
+    std::mutex pipe_mu;
+    hipStream_t stream = nullptr;
+    uint8_t *d_arena = nullptr, *d_side = nullptr;
+    size_t arena_cap = 0, side_cap = 0;
+    std::vector<uint8_t> h_stat;
+};
+
+RouteState *route_state_create() { return new RouteState(); }
+
+void route_state_destroy(RouteState *r) {
+    if (!r) return;
+    hipFree(r->d_table);
+    hipFree(r->d_counters);
+    hipFree(r->d_arena);
+    hipFree(r->d_side);
+    if (r->stream) hipStreamDestroy(r->stream);
+    delete r;
+}
+
+}  // namespace qgcm
+
+using namespace qgcm;
+
+namespace {
+
+int hip_rc(hipError_t e) { return e == hipSuccess ? QGCM_OK : QGCM_E_HIP; }
+
+int resolve(qgcm_ctx *ctx, bool outgoing, uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+            uint32_t *d_peer, qgcm_desc *d_descs, hipStream_t s) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
+    if (n && (!d_arena || !d_lens || !d_peer || !d_descs || stride == 0)) return QGCM_E_ARG;
+    if (((uintptr_t)d_arena & 3) || ((uintptr_t)d_lens & 3) || ((uintptr_t)d_peer & 3) || ((uintptr_t)d_descs & 15))
+        return QGCM_E_ARG;
+    std::lock_guard<std::mutex> g(r->mu);
+    if (!r->set) return QGCM_E_ARG;
+    if (n == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    RouteArgs a{};
+    a.table = r->d_table;
+    a.cap_mask = r->cap_mask;
+    a.net = r->net.net;
+    a.mask = r->net.mask;
+    a.gateway = r->net.gateway;
+    a.own_ip = r->net.own_ip;
+    a.arena = d_arena;
+    a.stride = stride;
+    a.n = n;
+    a.lens = d_lens;
+    a.peer = d_peer;
+    a.descs = d_descs;
+    return hip_rc(launch_route_resolve(outgoing, a, s));
+}
+
+template <typename T>
+bool grow(T *&p, size_t &cap, size_t need) {
+    if (need <= cap) return true;
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if (hipMalloc(&p, need) != hipSuccess) return false;
+    cap = need;
+    return true;
+}
+
+// Outgoing.pipeline / Incoming.pipeline for a batch in host memory: chunks of at most kRouteChunk packets,
+// copy in -> resolve -> seal or open -> account -> copy back, on one stream.
+int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                   const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
+    if (n && (!h_arena || !h_lens || !h_peer || stride == 0)) return QGCM_E_ARG;
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+    }
+    if (n == 0) return 0;
+    const bool gen = seal && h_nonces == QGCM_NONCES_GENERATE;
+    const bool non = seal && h_nonces && !gen;
+    std::lock_guard<std::mutex> pg(r->pipe_mu);
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
+        r->stream = nullptr;
+        return QGCM_E_HIP;
+    }
+    hipStream_t s = r->stream;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(kRouteChunk, n),
+                                                        std::max<uint64_t>(1, kRouteChunkBytes / stride));
+    // side buffer of a chunk: descriptors (16-B aligned first), lengths, peers, nonces, statuses
+    const size_t o_desc = 0, o_lens = o_desc + 16ull * chunk, o_peer = o_lens + 4ull * chunk,
+                 o_non = o_peer + 4ull * chunk, o_stat = o_non + 12ull * chunk, side = o_stat + chunk;
+    if (!grow(r->d_arena, r->arena_cap, (size_t)chunk * stride) || !grow(r->d_side, r->side_cap, side)) return QGCM_E_NOMEM;
+    r->h_stat.resize(chunk);
+    qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
+    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
+    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
+    uint8_t *d_non = r->d_side + o_non, *d_stat = r->d_side + o_stat;
+    int dropped = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+        const uint32_t cn = std::min(chunk, n - c0);
+        uint8_t *h = h_arena + (uint64_t)c0 * stride;
+        if (hipMemcpyAsync(r->d_arena, h, (size_t)cn * stride, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(d_lens, h_lens + c0, 4ull * cn, hipMemcpyHostToDevice, s) != hipSuccess ||
+            (non && hipMemcpyAsync(d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, s) != hipSuccess))
+            return QGCM_E_HIP;
+        int rc = resolve(ctx, seal, r->d_arena, stride, cn, d_lens, d_peer, d_descs, s);
+        if (rc == QGCM_OK)
+            rc = seal ? qgcm_seal_batch(ctx, r->d_arena, d_descs, cn, gen ? QGCM_NONCES_GENERATE : non ? d_non : nullptr, 4,
+                                        d_stat, s)
+                      : qgcm_open_batch(ctx, r->d_arena, d_descs, cn, 4, d_stat, s);
+        if (rc == QGCM_OK) rc = qgcm_route_account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, d_descs, d_stat, s);
+        if (rc == QGCM_OK &&
+            (hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess))
+            rc = QGCM_E_HIP;
+        if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
+        if (rc != QGCM_OK) return rc;
+        for (uint32_t i = 0; i < cn; ++i) {
+            const bool ok = r->h_stat[i] == 1;
+            const uint32_t len = h_lens[c0 + i];
+            // sealed: the datagram Raw[:4 + L + 28]; opened: the plaintext packet qgcm_tun_write_slots takes
+            h_lens[c0 + i] = !ok ? 0 : seal ? 4 + len + QGCM_OVERHEAD : len - 4 - QGCM_OVERHEAD;
+            if (h_status) h_status[c0 + i] = ok ? 1 : 0;
+            dropped += !ok;
+        }
+    }
+    return dropped;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qgcm_routes_set(qgcm_ctx *ctx, const qgcm_route *routes, uint32_t count, const qgcm_route_net *net) {
+    if (!ctx || !net || (count && !routes) || count > (1u << 30)) return QGCM_E_ARG;
+    const uint32_t max_keys = ctx_max_keys(ctx);
+    for (uint32_t i = 0; i < count; ++i)
+        if (routes[i].peer >= max_keys) return QGCM_E_ARG;
+    uint32_t cap = 2;
+    while (cap < 2ull * count) cap <<= 1;
+    std::vector<qgcm_route> table(cap, qgcm_route{0, QGCM_NO_PEER});
+    for (uint32_t i = 0; i < count; ++i) {
+        uint32_t h = route_hash(routes[i].ip) & (cap - 1);
+        while (table[h].peer != QGCM_NO_PEER && table[h].ip != routes[i].ip) h = (h + 1) & (cap - 1);
+        table[h] = routes[i];  // a duplicate ip takes the last entry, as a map assignment does
+    }
+    RouteState *r = ctx_route(ctx);
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    uint2 *fresh = nullptr, *old = nullptr;
+    if (hipMalloc(&fresh, (size_t)cap * 8) != hipSuccess) return QGCM_E_NOMEM;
+    if (hipMemcpy(fresh, table.data(), (size_t)cap * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        hipFree(fresh);
+        return QGCM_E_HIP;
+    }
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->d_counters) {
+            const size_t words = 4 * (1 + (size_t)max_keys);
+            if (hipMalloc(&r->d_counters, 2 * words * 8) != hipSuccess ||
+                hipMemset(r->d_counters, 0, 2 * words * 8) != hipSuccess) {
+                hipFree(r->d_counters);
+                r->d_counters = nullptr;
+                hipFree(fresh);
+                return QGCM_E_NOMEM;
+            }
+            r->dir_words = words;
+        }
+        old = r->d_table;
+        r->d_table = fresh;
+        r->cap_mask = cap - 1;
+        r->net = *net;
+        r->set = true;
+    }
+    if (old) hipFree(old);  // waits for the device: the launches that took `old` are done
+    return QGCM_OK;
+}
+
+int qgcm_resolve_outgoing(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+                          uint32_t *d_peer, qgcm_desc *d_descs, void *stream) {
+    return resolve(ctx, true, d_arena, stride, n, d_lens, d_peer, d_descs, (hipStream_t)stream);
+}
+
+int qgcm_resolve_incoming(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+                          uint32_t *d_peer, qgcm_desc *d_descs, void *stream) {
+    return resolve(ctx, false, const_cast<uint8_t *>(d_arena), stride, n, d_lens, d_peer, d_descs, (hipStream_t)stream);
+}
+
+int qgcm_route_account(qgcm_ctx *ctx, int dir, uint32_t n, const uint32_t *d_peer, const qgcm_desc *d_descs,
+                       const uint8_t *d_status, void *stream) {
+    if (!ctx || (dir != QGCM_TX && dir != QGCM_RX) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
+    if (n && (!d_peer || !d_descs)) return QGCM_E_ARG;
+    if (((uintptr_t)d_peer & 3) || ((uintptr_t)d_descs & 15)) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    RouteAccountArgs a{};
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+        a.counters = r->d_counters + (size_t)dir * r->dir_words;
+    }
+    if (n == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    a.max_keys = ctx_max_keys(ctx);
+    a.dir = dir;
+    a.n = n;
+    a.peer = d_peer;
+    a.descs = d_descs;
+    a.status = d_status;
+    return hip_rc(launch_route_account(a, ctx_num_cus(ctx), (hipStream_t)stream));
+}
+
+int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]) {
+    if (!ctx || !out || (dir != QGCM_TX && dir != QGCM_RX)) return QGCM_E_ARG;
+    if (peer != QGCM_NO_PEER && peer >= ctx_max_keys(ctx)) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    const unsigned long long *src;
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+        src = r->d_counters + (size_t)dir * r->dir_words + (peer == QGCM_NO_PEER ? 0 : 4 + 4ull * peer);
+    }
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    return hip_rc(hipMemcpy(out, src, 32, hipMemcpyDeviceToHost));
+}
+
+int qgcm_route_seal_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                         const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status) {
+    return run_route_host(ctx, true, h_arena, stride, n, h_lens, h_nonces, h_peer, h_status);
+}
+
+int qgcm_route_open_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                         uint32_t *h_peer, uint8_t *h_status) {
+    return run_route_host(ctx, false, h_arena, stride, n, h_lens, nullptr, h_peer, h_status);
+}
+
+}  // extern "C"

@@ -161,4 +161,48 @@ int qgcm_udp_send_slots(int fd, const uint8_t *arena, uint64_t stride, uint32_t 
     return (int)sent;
 }
 
+// socket/udp.go:43-47 with mapping.Sockaddr per packet: datagram i = Raw[:lens[i]] of slot i goes to
+// addrs[peer[i]] (what qgcm_route_seal_host left in h_lens and h_peer).  Packets with peer[i] ==
+// QGCM_NO_PEER or lens[i] == 0 (unroutable, or dropped by the seal) are skipped.  A peer[i] at or past
+// n_addrs fails the whole call before anything is sent.  Returns the number of datagrams sent, or -1.
+int qgcm_udp_send_slots_to(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
+                           const uint32_t *peer, const qgcm_peer_addr *addrs, uint32_t n_addrs) {
+    if (fd < 0 || (n && (!arena || !lens || !peer)) || (n_addrs && !addrs)) return -1;
+    for (uint32_t i = 0; i < n; ++i)
+        if (peer[i] != QGCM_NO_PEER && lens[i] != 0 && peer[i] >= n_addrs) return -1;
+    std::vector<mmsghdr> msgs(kVlen);
+    std::vector<iovec> iov(kVlen);
+    std::vector<sockaddr_in> dst(kVlen);
+    uint32_t next = 0, sent = 0;
+    while (next < n) {
+        unsigned k = 0;
+        for (; next < n && k < kVlen; ++next) {
+            if (peer[next] == QGCM_NO_PEER || lens[next] == 0) continue;
+            const qgcm_peer_addr &a = addrs[peer[next]];
+            memset(&dst[k], 0, sizeof dst[k]);
+            dst[k].sin_family = AF_INET;
+            dst[k].sin_addr.s_addr = a.ip;  // network byte order already
+            dst[k].sin_port = a.port;
+            iov[k] = iovec{const_cast<uint8_t *>(arena) + (uint64_t)next * stride,
+                           (size_t)std::min<uint64_t>(lens[next], stride)};
+            msgs[k] = mmsghdr{};
+            msgs[k].msg_hdr.msg_name = &dst[k];
+            msgs[k].msg_hdr.msg_namelen = sizeof dst[k];
+            msgs[k].msg_hdr.msg_iov = &iov[k];
+            msgs[k].msg_hdr.msg_iovlen = 1;
+            ++k;
+        }
+        for (unsigned done = 0; done < k;) {
+            const int r = sendmmsg(fd, msgs.data() + done, k - done, 0);
+            if (r < 0) {
+                if (errno == EINTR) continue;
+                return sent ? (int)sent : -1;
+            }
+            done += (unsigned)r;
+            sent += (uint32_t)r;
+        }
+    }
+    return (int)sent;
+}
+
 }  // extern "C"

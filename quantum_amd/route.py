@@ -1,0 +1,161 @@
+"""Routes: the per-packet Router of the reference restated over a dict, and thin wrappers of the batched
+route calls of libqgcm (include/qgcm.h "routes resolved on the GPU").
+
+common/common.go:42-45     IPtoInt
+router/router.go:21-31     Router.Resolve
+worker/outgoing.go:28-35   Outgoing.resolve  -> Router.outgoing
+worker/incoming.go:28-34   Incoming.resolve  -> Router.incoming
+metric/aggregator.go:24-32 Metrics{Packets, Bytes, DroppedPackets, DroppedBytes} -> route_stats
+
+The per-packet workers of worker.py take `resolve(payload) -> (payload, mapping, ok)`: give them
+Router.outgoing / Router.incoming.  Workers that batch call resolve_outgoing / resolve_incoming (device
+arenas) or route_seal_host / route_open_host (host arenas) instead; torch is used for device pointers and
+stream handles only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import socket
+import struct
+
+from . import _lib
+
+NO_PEER = _lib.NO_PEER
+TX, RX = _lib.TX, _lib.RX
+METRICS = ("Packets", "Bytes", "DroppedPackets", "DroppedBytes")
+
+
+def IPtoInt(ip: bytes) -> int:
+    """common/common.go:42-45: binary.LittleEndian.Uint32 of the four address bytes (a dotted string is
+    converted first, as net.ParseIP(...).To4() would)."""
+    if isinstance(ip, str):
+        ip = socket.inet_aton(ip)
+    if len(ip) != 4:
+        raise ValueError("IPtoInt takes an IPv4 address of 4 bytes")
+    return int.from_bytes(bytes(ip), "little")
+
+
+def mask_of(prefix: int) -> int:
+    """The IPtoInt value of a /prefix netmask (net.CIDRMask(prefix, 32))."""
+    if not 0 <= prefix <= 32:
+        raise ValueError("prefix must be in [0, 32]")
+    return IPtoInt(struct.pack(">I", (0xFFFFFFFF << (32 - prefix)) & 0xFFFFFFFF))
+
+
+class Router:
+    """router/router.go:15-31 over a dict: `mappings` maps IPtoInt(private IP) -> mapping (any object; the
+    batched table stores the peer's key slot), `net` / `mask` are cfg.NetworkConfig.IPNet, `gateway` the
+    datastore's gateway address (etcdv2.go:285-288) and `own_ip` cfg.PrivateIP, all IPtoInt values."""
+
+    def __init__(self, mappings: dict, net: int, mask: int, gateway: int, own_ip: int):
+        self.mappings, self.net, self.mask, self.gateway, self.own_ip = mappings, net, mask, gateway, own_ip
+
+    def Resolve(self, destination: bytes):
+        """router.go:21-31 -> (mapping, ok)."""
+        dip = IPtoInt(bytes(destination))
+        if (dip & self.mask) == (self.net & self.mask):  # IPNet.Contains
+            key = dip  # store.Mapping(dip)
+        else:
+            key = self.gateway  # store.GatewayMapping()
+        if key in self.mappings:
+            return self.mappings[key], True
+        return None, False
+
+    def outgoing(self, payload):
+        """worker/outgoing.go:28-35 -> (payload, mapping, ok)."""
+        mapping, ok = self.Resolve(bytes(payload.Raw[4 + 16:4 + 20]))  # payload.Packet[16:20]
+        if ok:
+            payload.Raw[0:4] = self.own_ip.to_bytes(4, "little")  # copy(payload.IPAddress, PrivateIP.To4())
+            return payload, mapping, True
+        return None, None, False
+
+    def incoming(self, payload):
+        """worker/incoming.go:28-34 -> (payload, mapping, ok)."""
+        mapping, ok = self.Resolve(bytes(payload.Raw[0:4]))  # payload.IPAddress
+        if ok:
+            return payload, mapping, True
+        return None, None, False
+
+    def install(self, ctx) -> None:
+        """The same table on ctx's GPU (the mappings' values must be key slots)."""
+        routes_set(ctx, self.mappings, self.net, self.mask, self.gateway, self.own_ip)
+
+
+def routes_set(ctx, routes, net: int, mask: int, gateway: int, own_ip: int) -> None:
+    """qgcm_routes_set: `routes` a dict or a sequence of (IPtoInt address, key slot) pairs; replaces the
+    context's whole table."""
+    pairs = list(routes.items()) if isinstance(routes, dict) else list(routes)
+    arr = (_lib.Route * max(1, len(pairs)))()
+    for i, (ip, peer) in enumerate(pairs):
+        arr[i].ip, arr[i].peer = ip, peer
+    rn = _lib.RouteNet(net, mask, gateway, own_ip)
+    _lib.check(_lib.lib().qgcm_routes_set(ctx.handle, C.addressof(arr), len(pairs), C.addressof(rn)), "qgcm_routes_set")
+
+
+def _stream_handle(stream) -> int:
+    import torch
+
+    s = stream if stream is not None else torch.cuda.current_stream()
+    return int(s.cuda_stream)
+
+
+def _ptr(t) -> int | None:
+    return None if t is None else int(t.data_ptr())
+
+
+def resolve_outgoing(ctx, arena, stride: int, n: int, lens, peer, descs, stream=None) -> None:
+    """qgcm_resolve_outgoing on device tensors: `lens` / `peer` int32 (n), `descs` uint8 (16 n bytes)."""
+    _lib.check(_lib.lib().qgcm_resolve_outgoing(ctx.handle, _ptr(arena), stride, n, _ptr(lens), _ptr(peer), _ptr(descs),
+                                                _stream_handle(stream)), "qgcm_resolve_outgoing")
+
+
+def resolve_incoming(ctx, arena, stride: int, n: int, lens, peer, descs, stream=None) -> None:
+    _lib.check(_lib.lib().qgcm_resolve_incoming(ctx.handle, _ptr(arena), stride, n, _ptr(lens), _ptr(peer), _ptr(descs),
+                                                _stream_handle(stream)), "qgcm_resolve_incoming")
+
+
+def route_account(ctx, direction: int, n: int, peer, descs, status=None, stream=None) -> None:
+    """qgcm_route_account: adds the batch to the context's Tx / Rx counters, after its seal / open on `stream`."""
+    _lib.check(_lib.lib().qgcm_route_account(ctx.handle, direction, n, _ptr(peer), _ptr(descs), _ptr(status),
+                                             _stream_handle(stream)), "qgcm_route_account")
+
+
+def route_stats(ctx, direction: int, peer: int = NO_PEER) -> dict[str, int]:
+    """qgcm_route_stats: metric.Metrics of one link, or of the totals (peer NO_PEER)."""
+    out = (C.c_uint64 * 4)()
+    _lib.check(_lib.lib().qgcm_route_stats(ctx.handle, direction, peer, C.addressof(out)), "qgcm_route_stats")
+    return dict(zip(METRICS, (int(v) for v in out)))
+
+
+def route_seal_host(ctx, arena_ptr: int, stride: int, n: int, lens, nonces, peer, status=None) -> int:
+    """qgcm_route_seal_host: `lens` / `peer` numpy uint32 arrays (lens updated to the datagram lengths),
+    `nonces` a host address, None or batch.GENERATE, `status` a numpy uint8 array or None.  Returns the
+    number of dropped packets."""
+    from .batch import GENERATE
+
+    np_ = _lib.NONCES_GENERATE if nonces is GENERATE else nonces
+    return _lib.check(_lib.lib().qgcm_route_seal_host(ctx.handle, arena_ptr, stride, n, lens.ctypes.data, np_,
+                                                      peer.ctypes.data, None if status is None else status.ctypes.data),
+                      "qgcm_route_seal_host")
+
+
+def route_open_host(ctx, arena_ptr: int, stride: int, n: int, lens, peer, status=None) -> int:
+    """qgcm_route_open_host: `lens` in as datagram lengths, out as plaintext packet lengths."""
+    return _lib.check(_lib.lib().qgcm_route_open_host(ctx.handle, arena_ptr, stride, n, lens.ctypes.data,
+                                                      peer.ctypes.data, None if status is None else status.ctypes.data),
+                      "qgcm_route_open_host")
+
+
+def peer_addrs(addrs) -> C.Array:
+    """A qgcm_peer_addr array from (dotted ip, port) pairs, index = key slot."""
+    arr = (_lib.PeerAddr * max(1, len(addrs)))()
+    for i, (ip, port) in enumerate(addrs):
+        arr[i].ip = struct.unpack("=I", socket.inet_aton(ip))[0]  # the address bytes in memory order, as s_addr
+        arr[i].port = socket.htons(port)
+    return arr
+
+
+def udp_send_slots_to(fd: int, arena_ptr: int, stride: int, n: int, lens, peer, addrs: C.Array, n_addrs: int) -> int:
+    """qgcm_udp_send_slots_to: datagram i to addrs[peer[i]]; returns the number sent or -1."""
+    return _lib.lib().qgcm_udp_send_slots_to(fd, arena_ptr, stride, n, lens.ctypes.data, peer.ctypes.data,
+                                             C.addressof(addrs), n_addrs)
