@@ -17,6 +17,9 @@
  *                         -> qgcm_routes_set + qgcm_resolve_outgoing / qgcm_resolve_incoming
  *   worker/outgoing.go:37-53 stats, metric/aggregator.go:24-68 -> qgcm_route_account / qgcm_route_stats
  *   Outgoing.pipeline / Incoming.pipeline for a batch         -> qgcm_route_seal_host / qgcm_route_open_host
+ *   main.go:41-51 plugin order, compression.go:31-33 / encryption.go:17-19 SupportedPlugins gate
+ *                         -> qgcm_peer_plugins_set + qgcm_chain_outgoing / qgcm_chain_incoming,
+ *                            qgcm_route_account_bytes, qgcm_route_chain_seal_host / qgcm_route_chain_open_host
  *   socket/udp.go:44-47 Write(payload, mapping)               -> qgcm_udp_send_slots_to
  *
  * Error convention follows the reference's own cgo layer (crypto/dtls.go:37-40, dtls.h:43-48):
@@ -519,6 +522,75 @@ int qgcm_route_seal_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint3
                          const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status);
 int qgcm_route_open_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
                          uint32_t *h_peer, uint8_t *h_status);
+/* ---- plugin chain on routed batches (main.go:41-51, plugin/compression.go, plugin/encryption.go) ---- */
+/* The reference decides per packet and per peer which plugins run: compression.go:31-33 and
+ * encryption.go:17-19 pass a packet through untouched when the peer's mapping.SupportedPlugins does not list
+ * the plugin, and main.go:41-51 runs the node's configured plugins in order: compression then encryption
+ * outgoing, the reverse incoming.  Here each key slot has one byte of plugin flags in device memory; the
+ * effective plugins of a packet are F = plugins & flags[peer], `plugins` being the node's own --plugins mask
+ * that every chain call takes.
+ *
+ * Every slot starts as QGCM_PLUGIN_ENCRYPTION, so a context that never calls qgcm_peer_plugins_set treats
+ * its peers as qgcm_route_seal_host / qgcm_route_open_host do.  set / get move count flag bytes of slots
+ * [first_idx, first_idx + count); a bit other than the two defined, or a range past max_keys: QGCM_E_ARG and
+ * nothing changes.  Synchronous.  A call sequence reads a packet's flags once and carries them with the
+ * packet in its work area: a qgcm_peer_plugins_set racing a batch changes each packet of it as a whole or
+ * not at all. */
+#define QGCM_PLUGIN_COMPRESSION 1u
+#define QGCM_PLUGIN_ENCRYPTION  2u
+int qgcm_peer_plugins_set(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, const uint8_t *flags);
+int qgcm_peer_plugins_get(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, uint8_t *flags);
+/* The chain of one batch, after qgcm_resolve_outgoing / qgcm_resolve_incoming on the same stream, with that
+ * call's d_lens, d_peer and d_descs (the descriptors are rewritten).  d_status (n bytes) and d_bytes (n
+ * uint32) receive each packet's verdict and the payload.Length that worker/outgoing.go:37-53 counts for it;
+ * d_work is QGCM_CHAIN_WORK(n) bytes of caller memory, 16-B aligned.  Arguments are checked as in the resolve
+ * calls (and plugins may hold only the two bits); n == 0 launches nothing; asynchronous on stream.  d_nonces
+ * takes the three forms of qgcm_seal_batch; with QGCM_NONCES_GENERATE packet j of the call owns nonce j of
+ * the reservation whether or not it ends up sealed.
+ *
+ * outgoing (d_lens[i] in: the TUN packet length L):
+ *   d_peer[i] == QGCM_NO_PEER or >= max_keys   slot untouched              d_lens 0      status 0  bytes 0
+ *   F has compression and the device codec     slot as resolve left it     d_lens 0      status 0  bytes 4 + L
+ *     refuses the packet: L > QGCM_SNAPPY_DEVICE_MAX, or a compressed form longer than
+ *     stride - 4 - (F has encryption ? 28 : 0) -- a divergence: snappy.Encode never fails
+ *   compression applied                        Raw[4:] <- the bytes of qgcm_snappy_compress, L <- their length
+ *   F has encryption, key slot unset           the (compressed) packet     d_lens 0      status 0  bytes 4 + L
+ *   F has encryption, sealed                   ct | tag | nonce under key  d_lens 4+L+28 status 1  bytes 4+L+28
+ *                                              `peer`, AAD Raw[0:4]
+ *   F has no encryption                        the (compressed) packet     d_lens 4 + L  status 1  bytes 4 + L
+ * d_lens out is the datagram length qgcm_udp_send_slots_to takes.
+ *
+ * incoming (d_lens[i] in: the datagram length m; encryption first, then compression):
+ *   unresolved                                                             d_lens 0      status 0  bytes 0
+ *   F has encryption and the open fails (tag, unset key, m - 4 < 28): the slot as qgcm_open_batch leaves it
+ *                                                                          d_lens 0      status 0  bytes m
+ *   F has compression and the decode fails (malformed, an empty result, longer than min(stride - 4,
+ *     QGCM_SNAPPY_DEVICE_MAX)): the slot keeps the packet the codec was given
+ *                                                                          d_lens 0      status 0  bytes 4 + the
+ *                                              length entering the plugin (m - 4 - 28 if opened, else m - 4)
+ *   delivered                                  the packet at Raw[4:]       d_lens = its length (what
+ *                                              qgcm_tun_write_slots takes) status 1  bytes 4 + that length
+ * d_status is authoritative: a delivered empty packet also has length 0. */
+#define QGCM_CHAIN_WORK(n) (4 * (((uint64_t)(n) + 15) & ~(uint64_t)15))
+int qgcm_chain_outgoing(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                        const uint32_t *d_peer, qgcm_desc *d_descs, uint32_t plugins, const uint8_t *d_nonces,
+                        uint8_t *d_status, uint32_t *d_bytes, void *d_work, void *stream);
+int qgcm_chain_incoming(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                        const uint32_t *d_peer, qgcm_desc *d_descs, uint32_t plugins,
+                        uint8_t *d_status, uint32_t *d_bytes, void *d_work, void *stream);
+/* qgcm_route_account with the byte counts of a chain call: the same counters, sums and on-chip combining.
+ * Unresolved (d_peer[i] == QGCM_NO_PEER or >= max_keys): totals DroppedPackets += 1; status 1: totals and
+ * link Packets += 1, Bytes += d_bytes[i]; any other status: DroppedPackets += 1, DroppedBytes += d_bytes[i].
+ * d_status NULL: every resolved packet was delivered. */
+int qgcm_route_account_bytes(qgcm_ctx *ctx, int dir, uint32_t n, const uint32_t *d_peer,
+                             const uint32_t *d_bytes, const uint8_t *d_status, void *stream);
+/* qgcm_route_seal_host / qgcm_route_open_host with the chain in place of the seal or open: the same chunks,
+ * the same one stream, the same serialisation; accounted with qgcm_route_account_bytes.  h_lens out is as in
+ * the tables above; returns the number of dropped packets or a negative error. */
+int qgcm_route_chain_seal_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                               const uint8_t *h_nonces, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status);
+int qgcm_route_chain_open_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                               uint32_t plugins, uint32_t *h_peer, uint8_t *h_status);
 /* socket/udp.go:44-47 with mapping.Sockaddr per packet: datagram i (Raw[:lens[i]] of slot i) goes to
  * addrs[peer[i]], in sendmmsg batches.  Packets with peer[i] == QGCM_NO_PEER or lens[i] == 0 are skipped.
  * Returns the number sent, or -1 (also, before anything is sent, when some peer[i] >= n_addrs). */

@@ -39,6 +39,8 @@ EXPORTS = (
     "qgcm_group_last_zerocopy", "qgcm_group_last_path", "qgcm_group_order", "qgcm_launch_counts", "qgcm_resident_stop", "qgcm_resident_stats",
     "qgcm_routes_set", "qgcm_resolve_outgoing", "qgcm_resolve_incoming", "qgcm_route_account", "qgcm_route_stats",
     "qgcm_route_seal_host", "qgcm_route_open_host", "qgcm_udp_send_slots_to",
+    "qgcm_peer_plugins_set", "qgcm_peer_plugins_get", "qgcm_chain_outgoing", "qgcm_chain_incoming",
+    "qgcm_route_account_bytes", "qgcm_route_chain_seal_host", "qgcm_route_chain_open_host",
 )
 
 QGCM_OK = 0
@@ -50,6 +52,14 @@ QGCM_E_NOMEM = -5
 OVERHEAD = 28
 NO_PEER = 0xFFFFFFFF  # QGCM_NO_PEER: a packet no route resolves, an empty route-table entry
 TX, RX = 0, 1  # QGCM_TX / QGCM_RX
+PLUGIN_COMPRESSION, PLUGIN_ENCRYPTION = 1, 2  # QGCM_PLUGIN_*: per-peer plugin flags, the node's own mask
+
+
+def chain_work(n: int) -> int:
+    """QGCM_CHAIN_WORK(n): bytes of work area a chain call of n packets takes (16-B aligned)."""
+    return 4 * ((n + 15) & ~15)
+
+
 QGCM_MAX_AAD = 16384  # longest additional data of a per-packet call (qgcm_seal_one / qgcm_open_one)
 ERRLEN = 120
 # QGCM_NONCES_GENERATE: as the nonce argument of a batch seal, "draw the nonces on the GPU from the
@@ -197,6 +207,14 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_route_seal_host.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp]
         L.qgcm_route_open_host.argtypes = [vp, vp, u64, u32, vp, vp, vp]
         L.qgcm_udp_send_slots_to.argtypes = [C.c_int, vp, u64, u32, vp, vp, vp, u32]
+    if hasattr(L, "qgcm_chain_outgoing"):  # (older builds loaded by the A/B tools lack the plugin chain)
+        L.qgcm_peer_plugins_set.argtypes = [vp, u32, u32, vp]
+        L.qgcm_peer_plugins_get.argtypes = [vp, u32, u32, vp]
+        L.qgcm_chain_outgoing.argtypes = [vp, vp, u64, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.qgcm_chain_incoming.argtypes = [vp, vp, u64, u32, vp, vp, vp, u32, vp, vp, vp, vp]
+        L.qgcm_route_account_bytes.argtypes = [vp, i32, u32, vp, vp, vp, vp]
+        L.qgcm_route_chain_seal_host.argtypes = [vp, vp, u64, u32, vp, vp, u32, vp, vp]
+        L.qgcm_route_chain_open_host.argtypes = [vp, vp, u64, u32, vp, u32, vp, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

@@ -224,11 +224,13 @@ struct SnapArgs {
     uint32_t n;
     uint32_t *lens;             // packet lengths, updated on success
     uint8_t *status;            // 1 ok / 0 failed, may be NULL
-    const uint8_t *status_in;   // uncompress: only packets whose status_in is 1 (NULL: all)
+    const uint8_t *status_in;   // only packets whose status_in is 1 (NULL: all); compress also takes 2:
+                                // output limit limit_b in place of limit (the plugin chain's gate)
     qgcm_desc *descs;           // compress: seal descriptors out {i * stride, len or QGCM_MAX_PAYLOAD, key}
     uint32_t key_idx;
     uint32_t max_in;            // packets longer than this fail
     uint32_t limit;             // compress: longest output kept; uncompress: output capacity
+    uint32_t limit_b;           // compress: ... of the packets whose status_in is 2 (at most limit)
     uint32_t sub;               // uncompress: lens[i] - sub is the compressed length (28 after an open)
     uint32_t off_in, off_out, off_sink, wave_bytes;  // off_sink: 256 B of per-lane scratch
 };
@@ -336,8 +338,45 @@ struct RouteAccountArgs {
     const uint32_t *peer;
     const qgcm_desc *descs;
     const uint8_t *status;         // NULL: every resolved packet was delivered
+    const uint32_t *bytes;         // NULL: the byte counts come from descs (len +- 28); else bytes[i] is
+                                   // the packet's count as it stands (qgcm_route_account_bytes; descs unused)
 };
 hipError_t launch_route_account(const RouteAccountArgs &a, int num_cus, hipStream_t s);
+// The plugin chain on routed batches (chain_kernels.hip; include/qgcm.h "plugin chain on routed batches"):
+// the elementwise kernels between resolve, the snappy codec, the descriptor seal / open and the accounting.
+// The work area (QGCM_CHAIN_WORK(n) bytes): four byte arrays of chain_work_lanes(n) entries each.
+//   flags: kChainResolved | (plugins & the peer's flags), 0 for an unresolved packet -- the one read of the
+//          peer's flags; every later stage of the call takes them from here
+//   gate:  the codec's status_in (outgoing: 1 compress, limit stride - 4; 2 compress, limit stride - 32;
+//          incoming: 1 uncompress; 0 not the codec's packet)
+//   cstat: the codec's status of the gated packets (0 before it runs)
+//   sstat: the seal's / open's status array
+constexpr uint32_t kChainResolved = 0x80;
+inline uint64_t chain_work_lanes(uint32_t n) { return ((uint64_t)n + 15) & ~15ull; }
+struct ChainArgs {
+    const uint8_t *peer_plugins;  // [max_keys]; NULL: every peer QGCM_PLUGIN_ENCRYPTION
+    uint32_t plugins;             // the node's own mask
+    uint32_t max_keys;
+    uint64_t stride;
+    uint32_t n;
+    uint32_t *lens;
+    const uint32_t *peer;
+    qgcm_desc *descs;             // 16-B aligned
+    uint8_t *status;
+    uint32_t *bytes;
+    uint8_t *flags, *gate, *cstat, *sstat;
+};
+// outgoing: kChainOutPlan (flags, gate; fused: the seal descriptors too, for a call without compression),
+// the codec, kChainOutDescs (seal descriptors of what the codec left sealable), the seal, kChainOutFinish.
+// incoming: kChainInPlan (flags, open descriptors), the open, kChainInMid (open verdicts, the codec's gate and
+// lengths; fused: takes the flags itself, for a call without encryption), the codec, kChainInFinish.
+enum ChainStage { kChainOutPlan, kChainOutDescs, kChainOutFinish, kChainInPlan, kChainInMid, kChainInFinish };
+hipError_t launch_chain(ChainStage stage, bool fused, const ChainArgs &a, hipStream_t s);
+// qgcm_api.cpp: the device codec over the packets a gate array selects (SnapArgs::status_in), statuses of
+// those packets into d_status; compress: gate 1 -> limit, gate 2 -> limit_b
+int run_snappy_gated(qgcm_ctx *ctx, bool compress, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                     uint32_t max_in, uint32_t limit, uint32_t limit_b, uint8_t *d_status, const uint8_t *d_gate,
+                     hipStream_t s);
 // The context's route state (route.cpp): made by qgcm_create, freed by qgcm_destroy after the device is idle.
 struct RouteState;
 RouteState *route_state_create();

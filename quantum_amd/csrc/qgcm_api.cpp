@@ -1451,7 +1451,7 @@ static int run_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride,
 // Device snappy batch (snappy_kernels.hip), defined below.
 static int run_snappy(qgcm_ctx *ctx, bool compress, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
                       uint32_t max_in, uint32_t limit, uint8_t *d_status, const uint8_t *d_status_in,
-                      qgcm_desc *d_descs, uint32_t key_idx, uint32_t sub, hipStream_t s);
+                      qgcm_desc *d_descs, uint32_t key_idx, uint32_t sub, hipStream_t s, uint32_t limit_b = 0);
 
 // Compression + Encryption chain over host batches (BASELINE config 5; plugin order main.go:50-51:
 // outgoing compression.go then encryption.go, incoming the reverse).  Chunks of ~32 MiB of slots go
@@ -1776,12 +1776,12 @@ static int run_host_chain(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t s
 // longest packet the call admits.
 static int run_snappy(qgcm_ctx *ctx, bool compress, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
                       uint32_t max_in, uint32_t limit, uint8_t *d_status, const uint8_t *d_status_in,
-                      qgcm_desc *d_descs, uint32_t key_idx, uint32_t sub, hipStream_t s) {
+                      qgcm_desc *d_descs, uint32_t key_idx, uint32_t sub, hipStream_t s, uint32_t limit_b) {
     // compress: inputs up to kSnapDevMax; uncompress: outputs up to kSnapDevMax, inputs up to the longest
     // stream such an output can have
     const uint64_t in_max = compress ? kSnapDevMax : qgcm_snappy_max_compressed_length(kSnapDevMax);
     if (!ctx || (n && (!d_arena || !d_lens)) || (stride & 3) || stride < 4 || max_in > in_max ||
-        max_in > stride - 4 || limit > stride - 4 || (!compress && limit > kSnapDevMax))
+        max_in > stride - 4 || limit > stride - 4 || (!compress && limit > kSnapDevMax) || limit_b > limit)
         return QGCM_E_ARG;
     if (n == 0) return QGCM_OK;
     auto a16 = [](uint32_t x) { return (x + 15u) & ~15u; };
@@ -1796,6 +1796,7 @@ static int run_snappy(qgcm_ctx *ctx, bool compress, uint8_t *d_arena, uint64_t s
     a.key_idx = key_idx;
     a.max_in = max_in;
     a.limit = limit;
+    a.limit_b = limit_b;  // the LDS regions below are sized by limit: limit_b is never larger
     a.sub = sub;
     uint32_t tab = 0;
     if (compress) {
@@ -1847,6 +1848,17 @@ static int run_snappy(qgcm_ctx *ctx, bool compress, uint8_t *d_arena, uint64_t s
     ctx->count(compress ? QGCM_KERNEL_SNAPPY_ENC : QGCM_KERNEL_SNAPPY_DEC);
     return hip_fail(launch_snappy(compress, a, waves, grid, s, group ? 1 : gdec ? 2 : 0));
 }
+
+}  // extern "C"
+
+int qgcm::run_snappy_gated(qgcm_ctx *ctx, bool compress, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                           uint32_t max_in, uint32_t limit, uint32_t limit_b, uint8_t *d_status, const uint8_t *d_gate,
+                           hipStream_t s) {
+    return run_snappy(ctx, compress, d_arena, stride, n, d_lens, max_in, limit, d_status, d_gate, nullptr, 0, 0, s,
+                      limit_b);
+}
+
+extern "C" {
 
 int qgcm_snappy_compress_batch(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
                                uint32_t max_len, uint32_t limit, uint8_t *d_status, qgcm_desc *d_descs_out,

@@ -31,6 +31,8 @@ struct RouteState {
     qgcm_route_net net{};
     unsigned long long *d_counters = nullptr;  // [2 directions][1 + max_keys][4]
     size_t dir_words = 0;                      // 4 * (1 + max_keys)
+    uint8_t *d_plugins = nullptr;  // [max_keys] per-peer plugin flags, made by the first qgcm_peer_plugins_set and
+                                   // kept until the context goes (NULL: every peer QGCM_PLUGIN_ENCRYPTION)
 
     // the routed host pipelines: one stream, device staging grown on demand, one call at a time
     std::mutex pipe_mu;
@@ -46,6 +48,7 @@ void route_state_destroy(RouteState *r) {
     if (!r) return;
     hipFree(r->d_table);
     hipFree(r->d_counters);
+    hipFree(r->d_plugins);
     hipFree(r->d_arena);
     hipFree(r->d_side);
     if (r->stream) hipStreamDestroy(r->stream);
@@ -99,14 +102,112 @@ bool grow(T *&p, size_t &cap, size_t need) {
     return true;
 }
 
+constexpr uint32_t kAllPlugins = QGCM_PLUGIN_COMPRESSION | QGCM_PLUGIN_ENCRYPTION;
+
+// The plugin chain between a resolve and the accounting, on s (qgcm_chain_outgoing / qgcm_chain_incoming).
+int run_chain(qgcm_ctx *ctx, bool outgoing, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+              const uint32_t *d_peer, qgcm_desc *d_descs, uint32_t plugins, const uint8_t *d_nonces, uint8_t *d_status,
+              uint32_t *d_bytes, void *d_work, hipStream_t s) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || n > QGCM_MAX_BATCH || (plugins & ~kAllPlugins)) return QGCM_E_ARG;
+    if (n && (!d_arena || !d_lens || !d_peer || !d_descs || !d_status || !d_bytes || !d_work || stride == 0))
+        return QGCM_E_ARG;
+    if (((uintptr_t)d_arena & 3) || ((uintptr_t)d_lens & 3) || ((uintptr_t)d_peer & 3) || ((uintptr_t)d_descs & 15) ||
+        ((uintptr_t)d_bytes & 3) || ((uintptr_t)d_work & 15))
+        return QGCM_E_ARG;
+    const bool gen = d_nonces == QGCM_NONCES_GENERATE;
+    if (outgoing && !gen && ((uintptr_t)d_nonces & 3)) return QGCM_E_ARG;
+    ChainArgs a{};
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+        a.peer_plugins = r->d_plugins;  // never freed or moved while the context lives
+    }
+    if (n == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    const uint64_t lanes = chain_work_lanes(n);
+    a.plugins = plugins;
+    a.max_keys = ctx_max_keys(ctx);
+    a.stride = stride;
+    a.n = n;
+    a.lens = d_lens;
+    a.peer = d_peer;
+    a.descs = d_descs;
+    a.status = d_status;
+    a.bytes = d_bytes;
+    a.flags = static_cast<uint8_t *>(d_work);
+    a.gate = a.flags + lanes;
+    a.cstat = a.gate + lanes;
+    a.sstat = a.cstat + lanes;
+    const bool comp = plugins & QGCM_PLUGIN_COMPRESSION, enc = plugins & QGCM_PLUGIN_ENCRYPTION;
+    // the device codec's reach: slots of stride - 4 packet bytes, at most QGCM_SNAPPY_DEVICE_MAX of them
+    const uint32_t room = (uint32_t)std::min<uint64_t>(stride - 4, QGCM_SNAPPY_DEVICE_MAX);
+    int rc;
+    if (outgoing) {
+        // a resolved packet has 4 + L + 28 <= stride; below 36 bytes of slot there is none
+        const bool codec = comp && stride >= 4 + 4 + QGCM_OVERHEAD;
+        rc = hip_rc(launch_chain(kChainOutPlan, enc && !codec, a, s));
+        if (rc == QGCM_OK && codec)
+            rc = run_snappy_gated(ctx, true, d_arena, stride, n, d_lens, room, room,
+                                  (uint32_t)std::min<uint64_t>(stride - 4 - QGCM_OVERHEAD, room), a.cstat, a.gate, s);
+        if (rc == QGCM_OK && enc && codec) rc = hip_rc(launch_chain(kChainOutDescs, false, a, s));
+        if (rc == QGCM_OK && enc) rc = qgcm_seal_batch(ctx, d_arena, d_descs, n, d_nonces, 4, a.sstat, s);
+        if (rc == QGCM_OK) rc = hip_rc(launch_chain(kChainOutFinish, false, a, s));
+        return rc;
+    }
+    rc = QGCM_OK;
+    if (enc) {
+        rc = hip_rc(launch_chain(kChainInPlan, false, a, s));
+        if (rc == QGCM_OK) rc = qgcm_open_batch(ctx, d_arena, d_descs, n, 4, a.sstat, s);
+    }
+    if (rc == QGCM_OK) rc = hip_rc(launch_chain(kChainInMid, !enc, a, s));
+    if (rc == QGCM_OK && comp) {
+        // stride 4 holds no packet byte: every gated packet is the empty stream, which does not decode
+        if (room)
+            rc = run_snappy_gated(ctx, false, d_arena, stride, n, d_lens,
+                                  (uint32_t)std::min<uint64_t>(stride - 4, qgcm_snappy_max_compressed_length(QGCM_SNAPPY_DEVICE_MAX)),
+                                  room, 0, a.cstat, a.gate, s);
+        if (rc == QGCM_OK) rc = hip_rc(launch_chain(kChainInFinish, false, a, s));
+    }
+    return rc;
+}
+
+int account(qgcm_ctx *ctx, int dir, uint32_t n, const uint32_t *d_peer, const qgcm_desc *d_descs, const uint32_t *d_bytes,
+            bool by_bytes, const uint8_t *d_status, hipStream_t s) {
+    if (!ctx || (dir != QGCM_TX && dir != QGCM_RX) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
+    if (n && (!d_peer || (by_bytes ? !d_bytes : !d_descs))) return QGCM_E_ARG;
+    if (((uintptr_t)d_peer & 3) || ((uintptr_t)d_descs & 15) || ((uintptr_t)d_bytes & 3)) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    RouteAccountArgs a{};
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+        a.counters = r->d_counters + (size_t)dir * r->dir_words;
+    }
+    if (n == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    a.max_keys = ctx_max_keys(ctx);
+    a.dir = dir;
+    a.n = n;
+    a.peer = d_peer;
+    a.descs = d_descs;
+    a.status = d_status;
+    a.bytes = by_bytes ? d_bytes : nullptr;
+    return hip_rc(launch_route_account(a, ctx_num_cus(ctx), s));
+}
+
 // Outgoing.pipeline / Incoming.pipeline for a batch in host memory: chunks of at most kRouteChunk packets,
-// copy in -> resolve -> seal or open -> account -> copy back, on one stream.
+// copy in -> resolve -> seal or open (chain: the plugin chain under the node's `plugins`) -> account -> copy
+// back, on one stream.
 int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
-                   const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status) {
+                   const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status, bool chain = false,
+                   uint32_t plugins = 0) {
     if (!ctx) return QGCM_E_ARG;
     RouteState *r = ctx_route(ctx);
     if ((stride & 3) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
     if (n && (!h_arena || !h_lens || !h_peer || stride == 0)) return QGCM_E_ARG;
+    if (chain && (plugins & ~kAllPlugins)) return QGCM_E_ARG;
     {
         std::lock_guard<std::mutex> g(r->mu);
         if (!r->set) return QGCM_E_ARG;
@@ -123,15 +224,19 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
     hipStream_t s = r->stream;
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(kRouteChunk, n),
                                                         std::max<uint64_t>(1, kRouteChunkBytes / stride));
-    // side buffer of a chunk: descriptors (16-B aligned first), lengths, peers, nonces, statuses
+    // side buffer of a chunk: descriptors (16-B aligned first), lengths, peers, nonces, statuses; the chain's
+    // byte counts and its work area (16-B aligned) behind them
     const size_t o_desc = 0, o_lens = o_desc + 16ull * chunk, o_peer = o_lens + 4ull * chunk,
-                 o_non = o_peer + 4ull * chunk, o_stat = o_non + 12ull * chunk, side = o_stat + chunk;
+                 o_non = o_peer + 4ull * chunk, o_stat = o_non + 12ull * chunk,
+                 o_bytes = (o_stat + chunk + 15) & ~(size_t)15, o_work = o_bytes + 4 * (size_t)chain_work_lanes(chunk),
+                 side = chain ? o_work + QGCM_CHAIN_WORK(chunk) : o_stat + chunk;
     if (!grow(r->d_arena, r->arena_cap, (size_t)chunk * stride) || !grow(r->d_side, r->side_cap, side)) return QGCM_E_NOMEM;
     r->h_stat.resize(chunk);
     qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
     uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
     uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
     uint8_t *d_non = r->d_side + o_non, *d_stat = r->d_side + o_stat;
+    uint32_t *d_bytes = reinterpret_cast<uint32_t *>(r->d_side + o_bytes);
     int dropped = 0;
     for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
         const uint32_t cn = std::min(chunk, n - c0);
@@ -141,20 +246,32 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
             (non && hipMemcpyAsync(d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, s) != hipSuccess))
             return QGCM_E_HIP;
         int rc = resolve(ctx, seal, r->d_arena, stride, cn, d_lens, d_peer, d_descs, s);
-        if (rc == QGCM_OK)
-            rc = seal ? qgcm_seal_batch(ctx, r->d_arena, d_descs, cn, gen ? QGCM_NONCES_GENERATE : non ? d_non : nullptr, 4,
-                                        d_stat, s)
+        const uint8_t *nonces = gen ? QGCM_NONCES_GENERATE : non ? d_non : nullptr;
+        if (rc == QGCM_OK && chain) {
+            rc = run_chain(ctx, seal, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, nonces, d_stat, d_bytes,
+                           r->d_side + o_work, s);
+            if (rc == QGCM_OK) rc = account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
+        } else if (rc == QGCM_OK) {
+            rc = seal ? qgcm_seal_batch(ctx, r->d_arena, d_descs, cn, nonces, 4, d_stat, s)
                       : qgcm_open_batch(ctx, r->d_arena, d_descs, cn, 4, d_stat, s);
-        if (rc == QGCM_OK) rc = qgcm_route_account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, d_descs, d_stat, s);
+            if (rc == QGCM_OK) rc = qgcm_route_account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, d_descs, d_stat, s);
+        }
         if (rc == QGCM_OK &&
             (hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess ||
              hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess))
+             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             // the chain's lengths are final on the device (the tables of include/qgcm.h)
+             (chain && hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess)))
             rc = QGCM_E_HIP;
         if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
         if (rc != QGCM_OK) return rc;
         for (uint32_t i = 0; i < cn; ++i) {
             const bool ok = r->h_stat[i] == 1;
+            if (chain) {
+                if (h_status) h_status[c0 + i] = ok ? 1 : 0;
+                dropped += !ok;
+                continue;
+            }
             const uint32_t len = h_lens[c0 + i];
             // sealed: the datagram Raw[:4 + L + 28]; opened: the plaintext packet qgcm_tun_write_slots takes
             h_lens[c0 + i] = !ok ? 0 : seal ? 4 + len + QGCM_OVERHEAD : len - 4 - QGCM_OVERHEAD;
@@ -225,25 +342,63 @@ int qgcm_resolve_incoming(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride
 
 int qgcm_route_account(qgcm_ctx *ctx, int dir, uint32_t n, const uint32_t *d_peer, const qgcm_desc *d_descs,
                        const uint8_t *d_status, void *stream) {
-    if (!ctx || (dir != QGCM_TX && dir != QGCM_RX) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
-    if (n && (!d_peer || !d_descs)) return QGCM_E_ARG;
-    if (((uintptr_t)d_peer & 3) || ((uintptr_t)d_descs & 15)) return QGCM_E_ARG;
+    return account(ctx, dir, n, d_peer, d_descs, nullptr, false, d_status, (hipStream_t)stream);
+}
+
+int qgcm_route_account_bytes(qgcm_ctx *ctx, int dir, uint32_t n, const uint32_t *d_peer, const uint32_t *d_bytes,
+                             const uint8_t *d_status, void *stream) {
+    return account(ctx, dir, n, d_peer, nullptr, d_bytes, true, d_status, (hipStream_t)stream);
+}
+
+int qgcm_peer_plugins_set(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, const uint8_t *flags) {
+    if (!ctx || (count && !flags)) return QGCM_E_ARG;
+    const uint32_t max_keys = ctx_max_keys(ctx);
+    if ((uint64_t)first_idx + count > max_keys) return QGCM_E_ARG;
+    for (uint32_t i = 0; i < count; ++i)
+        if (flags[i] & ~kAllPlugins) return QGCM_E_ARG;
+    if (count == 0) return QGCM_OK;
     RouteState *r = ctx_route(ctx);
-    RouteAccountArgs a{};
-    {
-        std::lock_guard<std::mutex> g(r->mu);
-        if (!r->set) return QGCM_E_ARG;
-        a.counters = r->d_counters + (size_t)dir * r->dir_words;
-    }
-    if (n == 0) return QGCM_OK;
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
-    a.max_keys = ctx_max_keys(ctx);
-    a.dir = dir;
-    a.n = n;
-    a.peer = d_peer;
-    a.descs = d_descs;
-    a.status = d_status;
-    return hip_rc(launch_route_account(a, ctx_num_cus(ctx), (hipStream_t)stream));
+    std::lock_guard<std::mutex> g(r->mu);
+    if (!r->d_plugins) {
+        uint8_t *fresh = nullptr;
+        if (hipMalloc(&fresh, max_keys) != hipSuccess) return QGCM_E_NOMEM;
+        if (hipMemset(fresh, QGCM_PLUGIN_ENCRYPTION, max_keys) != hipSuccess) {
+            hipFree(fresh);
+            return QGCM_E_HIP;
+        }
+        r->d_plugins = fresh;
+    }
+    // a batch in flight reads each packet's byte once (chain_kernels.hip): it sees the old or the new value
+    return hip_rc(hipMemcpy(r->d_plugins + first_idx, flags, count, hipMemcpyHostToDevice));
+}
+
+int qgcm_peer_plugins_get(qgcm_ctx *ctx, uint32_t first_idx, uint32_t count, uint8_t *flags) {
+    if (!ctx || (count && !flags)) return QGCM_E_ARG;
+    if ((uint64_t)first_idx + count > ctx_max_keys(ctx)) return QGCM_E_ARG;
+    if (count == 0) return QGCM_OK;
+    RouteState *r = ctx_route(ctx);
+    std::lock_guard<std::mutex> g(r->mu);
+    if (!r->d_plugins) {
+        memset(flags, QGCM_PLUGIN_ENCRYPTION, count);
+        return QGCM_OK;
+    }
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    return hip_rc(hipMemcpy(flags, r->d_plugins + first_idx, count, hipMemcpyDeviceToHost));
+}
+
+int qgcm_chain_outgoing(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                        const uint32_t *d_peer, qgcm_desc *d_descs, uint32_t plugins, const uint8_t *d_nonces,
+                        uint8_t *d_status, uint32_t *d_bytes, void *d_work, void *stream) {
+    return run_chain(ctx, true, d_arena, stride, n, d_lens, d_peer, d_descs, plugins, d_nonces, d_status, d_bytes, d_work,
+                     (hipStream_t)stream);
+}
+
+int qgcm_chain_incoming(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                        const uint32_t *d_peer, qgcm_desc *d_descs, uint32_t plugins, uint8_t *d_status,
+                        uint32_t *d_bytes, void *d_work, void *stream) {
+    return run_chain(ctx, false, d_arena, stride, n, d_lens, d_peer, d_descs, plugins, nullptr, d_status, d_bytes, d_work,
+                     (hipStream_t)stream);
 }
 
 int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]) {
@@ -268,6 +423,16 @@ int qgcm_route_seal_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint3
 int qgcm_route_open_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
                          uint32_t *h_peer, uint8_t *h_status) {
     return run_route_host(ctx, false, h_arena, stride, n, h_lens, nullptr, h_peer, h_status);
+}
+
+int qgcm_route_chain_seal_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                               const uint8_t *h_nonces, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status) {
+    return run_route_host(ctx, true, h_arena, stride, n, h_lens, h_nonces, h_peer, h_status, true, plugins);
+}
+
+int qgcm_route_chain_open_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                               uint32_t plugins, uint32_t *h_peer, uint8_t *h_status) {
+    return run_route_host(ctx, false, h_arena, stride, n, h_lens, nullptr, h_peer, h_status, true, plugins);
 }
 
 }  // extern "C"

@@ -14,7 +14,8 @@
 // them almost always), the rest and the waves' sums go through a 256-entry table in LDS keyed by peer
 // (entry peer & 255; a second peer on a taken entry goes to global memory directly), and a workgroup
 // walks several 256-packet tiles before it flushes the table, so a hot link costs two global atomics per
-// workgroup, not per packet.
+// workgroup, not per packet.  The byte counts come from the descriptors (qgcm_route_account) or from an array
+// (qgcm_route_account_bytes): one kernel, a template parameter.
 #include "gcm_internal.h"
 
 namespace qgcm {
@@ -88,6 +89,9 @@ __device__ __forceinline__ void acct_add(AcctLds &l, unsigned long long *links, 
     if (db) atomicAdd(dst + 3, db);
 }
 
+// kBytes: the byte count of packet i is a.bytes[i] as it stands (qgcm_route_account_bytes: the plugin chain
+// knows what each packet ended up as) instead of the descriptor's length +- tag and nonce
+template <bool kBytes>
 __global__ void __launch_bounds__(kRouteThreads) route_account_kernel(RouteAccountArgs a, uint32_t ntiles) {
     __shared__ AcctLds l;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
@@ -105,7 +109,10 @@ __global__ void __launch_bounds__(kRouteThreads) route_account_kernel(RouteAccou
         const bool resolved = in && p != QGCM_NO_PEER;
         bool ok = false;
         unsigned long long by = 0, db = 0;
-        if (resolved) {
+        if (resolved && kBytes) {
+            ok = a.status ? a.status[i] == 1 : true;
+            (ok ? by : db) = a.bytes[i];
+        } else if (resolved) {
             const uint32_t len = reinterpret_cast<const uint4 *>(a.descs + i)->z;
             ok = a.status ? a.status[i] == 1 : true;
             if (a.dir == QGCM_RX && len < QGCM_OVERHEAD) ok = false;  // shorter than tag and nonce: open rejects it
@@ -166,7 +173,11 @@ hipError_t launch_route_account(const RouteAccountArgs &a, int num_cus, hipStrea
     if (a.n == 0) return hipSuccess;
     const uint32_t ntiles = (uint32_t)(((uint64_t)a.n + kRouteThreads - 1) / kRouteThreads);
     const uint32_t cap = (uint32_t)(num_cus > 0 ? num_cus : 1) * kAcctWgsPerCu;
-    hipLaunchKernelGGL(route_account_kernel, dim3(ntiles < cap ? ntiles : cap), dim3(kRouteThreads), 0, s, a, ntiles);
+    const dim3 grid(ntiles < cap ? ntiles : cap);
+    if (a.bytes)
+        hipLaunchKernelGGL(route_account_kernel<true>, grid, dim3(kRouteThreads), 0, s, a, ntiles);
+    else
+        hipLaunchKernelGGL(route_account_kernel<false>, grid, dim3(kRouteThreads), 0, s, a, ntiles);
     return hipGetLastError();
 }
 

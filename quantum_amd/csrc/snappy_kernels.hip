@@ -251,10 +251,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) s
     if (p < a.n) pf_issue(f, a, p, lane, cover);
     for (; p < a.n; p += step) {
         const uint32_t len = rfl(f.len);
+        // status_in (the plugin chain's gate): 1 = code the packet, output limit a.limit; 2 = code it, limit
+        // a.limit_b; anything else = not this codec's packet: slot, length and status untouched
+        const uint32_t gate = rfl(f.st);
+        const bool take = gate == 1 || gate == 2;
+        const uint32_t lim = gate == 2 ? a.limit_b : a.limit;
         uint8_t *slot = a.arena + (uint64_t)p * a.stride;
-        bool ok = len <= a.max_in;
+        bool ok = take && len <= a.max_in;
         if (ok) stage_in(w.in, slot, len, lane, cover, f);
         if (p + step < a.n) pf_issue(f, a, p + step, lane, cover);  // in flight while this packet is coded
+        if (!take) continue;  // wave-uniform; nothing of this packet is in LDS
         uint32_t d = 0;
         if (ok) {
             wave_lds_sync();
@@ -267,7 +273,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) s
                 op = encode_block(w, op, len, bits);
             }
             d = op;
-            ok = d <= a.limit;
+            ok = d <= lim;
             wave_lds_sync();
             if (ok) write_out(slot, w.out, d, lane);
         }
@@ -516,12 +522,20 @@ __global__ void __launch_bounds__(256) snappy_compress_group_kernel(SnapArgs a) 
         const uint32_t p = p0 + grp;
         const bool have = p < a.n;
         const uint32_t len = have ? f.len : 0u;
+        // status_in (the plugin chain's gate), per group: 1 = code the packet, output limit a.limit; 2 = code
+        // it, limit a.limit_b; anything else = not this codec's packet: slot, length and status untouched.  A
+        // gated-off group idles under the exec mask like the groups past n: every wave_lds_sync below is
+        // outside the per-group branches, so the whole wave reaches it whatever its groups' gates.
+        const uint32_t gate = have ? f.st : 0u;
+        const bool take = gate == 1 || gate == 2;
+        const uint32_t lim = gate == 2 ? a.limit_b : a.limit;
         uint8_t *slot = a.arena + (uint64_t)(have ? p : 0u) * a.stride;
-        bool ok = have && len <= a.max_in;
+        bool ok = take && len <= a.max_in;
         // max(len, limit) bytes staged: the restore copy of a packet whose output overflows
-        if (ok) gstage(w.in, slot, max(len, a.limit), gl, cover, f);  // 4-B aligned slot, stride a multiple of 4
-        gpf_issue(f, a, p + step, gl, cover);                         // in flight while these packets are coded
+        if (ok) gstage(w.in, slot, max(len, lim), gl, cover, f);  // 4-B aligned slot, stride a multiple of 4
+        gpf_issue(f, a, p + step, gl, cover);                     // in flight while these packets are coded
         w.out = slot + 4;
+        w.olast = lim - 1;
         wave_lds_sync();
         uint32_t d = 0;
         if (ok) {
@@ -539,18 +553,18 @@ __global__ void __launch_bounds__(256) snappy_compress_group_kernel(SnapArgs a) 
                 op = gencode_block(w, op, len, bits);
             }
             d = op;
-            ok = d <= a.limit;
+            ok = d <= lim;
             if (!ok) {  // overflowed: the slot's first `limit` bytes back from the staged copy
                 uint32_t *dst = reinterpret_cast<uint32_t *>(slot + 4);
                 const uint32_t *srcw = reinterpret_cast<const uint32_t *>(w.in);
-                const uint32_t nw = a.limit >> 2;
+                const uint32_t nw = lim >> 2;
                 for (uint32_t j = gl; j < nw; j += kGL) dst[j] = srcw[j];
-                const uint32_t t = a.limit & 3;
+                const uint32_t t = lim & 3;
                 if (gl < t) slot[4 + 4 * nw + gl] = w.in[4 * nw + gl];
             }
         }
         wave_lds_sync();
-        if (have && gl == 0) {
+        if (take && gl == 0) {
             if (ok) a.lens[p] = d;
             if (a.status) a.status[p] = ok ? 1 : 0;
             if (a.descs) a.descs[p] = qgcm_desc{(uint64_t)p * a.stride, ok ? d : QGCM_MAX_PAYLOAD, a.key_idx};

@@ -11,6 +11,9 @@ The per-packet workers of worker.py take `resolve(payload) -> (payload, mapping,
 Router.outgoing / Router.incoming.  Workers that batch call resolve_outgoing / resolve_incoming (device
 arenas) or route_seal_host / route_open_host (host arenas) instead; torch is used for device pointers and
 stream handles only.
+
+main.go:41-51              the node's plugins in order  -> Router(plugins=...), chain_outgoing / chain_incoming
+plugin/compression.go:31-33, plugin/encryption.go:17-19  the per-peer gate -> peer_plugins_set, plugin_flags
 """
 from __future__ import annotations
 
@@ -22,6 +25,7 @@ from . import _lib
 
 NO_PEER = _lib.NO_PEER
 TX, RX = _lib.TX, _lib.RX
+PLUGIN_COMPRESSION, PLUGIN_ENCRYPTION = _lib.PLUGIN_COMPRESSION, _lib.PLUGIN_ENCRYPTION
 METRICS = ("Packets", "Bytes", "DroppedPackets", "DroppedBytes")
 
 
@@ -45,10 +49,38 @@ def mask_of(prefix: int) -> int:
 class Router:
     """router/router.go:15-31 over a dict: `mappings` maps IPtoInt(private IP) -> mapping (any object; the
     batched table stores the peer's key slot), `net` / `mask` are cfg.NetworkConfig.IPNet, `gateway` the
-    datastore's gateway address (etcdv2.go:285-288) and `own_ip` cfg.PrivateIP, all IPtoInt values."""
+    datastore's gateway address (etcdv2.go:285-288) and `own_ip` cfg.PrivateIP, all IPtoInt values.
 
-    def __init__(self, mappings: dict, net: int, mask: int, gateway: int, own_ip: int):
+    `plugins` (optional): the node's own plugins, names or quantum_amd.plugin objects (main.go:41-45).  With
+    them outgoing / incoming are the worker's whole pipeline stage (worker/outgoing.go:55-93): resolve, then
+    every plugin's Apply in the reference's order -- compression before encryption outgoing, the reverse
+    incoming (main.go:46-51) -- each gated by the mapping's own SupportedPlugins, so the mappings must be
+    common.Mapping objects.  A plugin that drops the packet ends the chain: (payload, mapping, False), the
+    payload's Length as that plugin left it (what outgoing.go:37-53 counts)."""
+
+    def __init__(self, mappings: dict, net: int, mask: int, gateway: int, own_ip: int, plugins=None):
         self.mappings, self.net, self.mask, self.gateway, self.own_ip = mappings, net, mask, gateway, own_ip
+        self.plugins = None
+        if plugins is not None:
+            from . import plugin as P
+
+            made = []
+            for p in plugins:
+                if isinstance(p, str):
+                    p, err = P.New(p)
+                    if err is not None:
+                        raise err
+                made.append(p)
+            self.plugins = (P.Sorter(made), P.Sorter(made, reverse=True))  # outgoing, incoming
+
+    def _apply(self, direction: int, payload, mapping):
+        from . import plugin as P
+
+        for p in self.plugins[0 if direction == P.Outgoing else 1]:
+            payload, mapping, ok = p.Apply(direction, payload, mapping)
+            if not ok:
+                return payload, mapping, False
+        return payload, mapping, True
 
     def Resolve(self, destination: bytes):
         """router.go:21-31 -> (mapping, ok)."""
@@ -66,6 +98,8 @@ class Router:
         mapping, ok = self.Resolve(bytes(payload.Raw[4 + 16:4 + 20]))  # payload.Packet[16:20]
         if ok:
             payload.Raw[0:4] = self.own_ip.to_bytes(4, "little")  # copy(payload.IPAddress, PrivateIP.To4())
+            if self.plugins is not None:
+                return self._apply(1, payload, mapping)  # plugin.Outgoing
             return payload, mapping, True
         return None, None, False
 
@@ -73,6 +107,8 @@ class Router:
         """worker/incoming.go:28-34 -> (payload, mapping, ok)."""
         mapping, ok = self.Resolve(bytes(payload.Raw[0:4]))  # payload.IPAddress
         if ok:
+            if self.plugins is not None:
+                return self._apply(0, payload, mapping)  # plugin.Incoming
             return payload, mapping, True
         return None, None, False
 
@@ -144,6 +180,79 @@ def route_open_host(ctx, arena_ptr: int, stride: int, n: int, lens, peer, status
     return _lib.check(_lib.lib().qgcm_route_open_host(ctx.handle, arena_ptr, stride, n, lens.ctypes.data,
                                                       peer.ctypes.data, None if status is None else status.ctypes.data),
                       "qgcm_route_open_host")
+
+
+def plugin_flags(names) -> int:
+    """The QGCM_PLUGIN_* mask of a SupportedPlugins / --plugins list (other names, such as "mock", have no
+    device stage and no bit)."""
+    names = list(names or [])
+    return (PLUGIN_COMPRESSION if "compression" in names else 0) | (PLUGIN_ENCRYPTION if "encryption" in names else 0)
+
+
+def peer_plugins_set(ctx, first: int, flags) -> None:
+    """qgcm_peer_plugins_set: `flags` one QGCM_PLUGIN_* mask per key slot from `first` on (bytes or ints)."""
+    buf = bytes(flags)
+    _lib.check(_lib.lib().qgcm_peer_plugins_set(ctx.handle, first, len(buf), C.c_char_p(buf) if buf else None),
+               "qgcm_peer_plugins_set")
+
+
+def peer_plugins_get(ctx, first: int, count: int) -> bytes:
+    """qgcm_peer_plugins_get: the masks of key slots [first, first + count)."""
+    out = C.create_string_buffer(max(1, count))
+    _lib.check(_lib.lib().qgcm_peer_plugins_get(ctx.handle, first, count, C.addressof(out)), "qgcm_peer_plugins_get")
+    return out.raw[:count]
+
+
+def chain_work(n: int, device="cuda"):
+    """A work area for a chain call of n packets (QGCM_CHAIN_WORK(n) bytes; torch allocations are 16-B aligned)."""
+    import torch
+
+    return torch.empty(max(16, _lib.chain_work(n)), dtype=torch.uint8, device=device)
+
+
+def chain_outgoing(ctx, arena, stride: int, n: int, lens, peer, descs, plugins: int, nonces, status, nbytes, work,
+                   stream=None) -> None:
+    """qgcm_chain_outgoing after resolve_outgoing on the same stream: `nonces` a device tensor, None or
+    batch.GENERATE; `status` uint8 (n), `nbytes` int32 (n), `work` from chain_work(n)."""
+    from .batch import GENERATE
+
+    np_ = _lib.NONCES_GENERATE if nonces is GENERATE else _ptr(nonces)
+    _lib.check(_lib.lib().qgcm_chain_outgoing(ctx.handle, _ptr(arena), stride, n, _ptr(lens), _ptr(peer), _ptr(descs),
+                                              plugins, np_, _ptr(status), _ptr(nbytes), _ptr(work),
+                                              _stream_handle(stream)), "qgcm_chain_outgoing")
+
+
+def chain_incoming(ctx, arena, stride: int, n: int, lens, peer, descs, plugins: int, status, nbytes, work,
+                   stream=None) -> None:
+    """qgcm_chain_incoming after resolve_incoming on the same stream."""
+    _lib.check(_lib.lib().qgcm_chain_incoming(ctx.handle, _ptr(arena), stride, n, _ptr(lens), _ptr(peer), _ptr(descs),
+                                              plugins, _ptr(status), _ptr(nbytes), _ptr(work), _stream_handle(stream)),
+               "qgcm_chain_incoming")
+
+
+def route_account_bytes(ctx, direction: int, n: int, peer, nbytes, status=None, stream=None) -> None:
+    """qgcm_route_account_bytes: route_account with the byte counts a chain call wrote."""
+    _lib.check(_lib.lib().qgcm_route_account_bytes(ctx.handle, direction, n, _ptr(peer), _ptr(nbytes), _ptr(status),
+                                                   _stream_handle(stream)), "qgcm_route_account_bytes")
+
+
+def route_chain_seal_host(ctx, arena_ptr: int, stride: int, n: int, lens, nonces, plugins: int, peer, status=None) -> int:
+    """qgcm_route_chain_seal_host: route_seal_host with the plugin chain under the node's `plugins` mask."""
+    from .batch import GENERATE
+
+    np_ = _lib.NONCES_GENERATE if nonces is GENERATE else nonces
+    return _lib.check(_lib.lib().qgcm_route_chain_seal_host(ctx.handle, arena_ptr, stride, n, lens.ctypes.data, np_,
+                                                            plugins, peer.ctypes.data,
+                                                            None if status is None else status.ctypes.data),
+                      "qgcm_route_chain_seal_host")
+
+
+def route_chain_open_host(ctx, arena_ptr: int, stride: int, n: int, lens, plugins: int, peer, status=None) -> int:
+    """qgcm_route_chain_open_host: `lens` in as datagram lengths, out as delivered packet lengths."""
+    return _lib.check(_lib.lib().qgcm_route_chain_open_host(ctx.handle, arena_ptr, stride, n, lens.ctypes.data,
+                                                            plugins, peer.ctypes.data,
+                                                            None if status is None else status.ctypes.data),
+                      "qgcm_route_chain_open_host")
 
 
 def peer_addrs(addrs) -> C.Array:
