@@ -20,7 +20,8 @@
  *   main.go:41-51 plugin order, compression.go:31-33 / encryption.go:17-19 SupportedPlugins gate
  *                         -> qgcm_peer_plugins_set + qgcm_chain_outgoing / qgcm_chain_incoming,
  *                            qgcm_route_account_bytes, qgcm_route_chain_seal_host / qgcm_route_chain_open_host
- *   socket/udp.go:44-47 Write(payload, mapping)               -> qgcm_udp_send_slots_to
+ *   socket/udp.go:44-47 Write(payload, mapping)               -> qgcm_udp_send_slots_to, or grouped per peer:
+ *                                                                qgcm_send_plan + qgcm_udp_send_plan
  *
  * Error convention follows the reference's own cgo layer (crypto/dtls.go:37-40, dtls.h:43-48):
  * constructors return NULL and fill a caller-supplied error buffer; everything else returns
@@ -597,6 +598,73 @@ int qgcm_route_chain_open_host(qgcm_ctx *ctx, uint8_t *h_arena, uint64_t stride,
 typedef struct qgcm_peer_addr { uint32_t ip; uint16_t port; uint16_t pad; } qgcm_peer_addr; /* network byte order */
 int qgcm_udp_send_slots_to(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
                            const uint32_t *peer, const qgcm_peer_addr *addrs, uint32_t n_addrs);
+
+/* ---- send plan on routed batches: per-peer segmented UDP sends ---- */
+/* With the UDP_SEGMENT control message one sendmsg carries many datagrams of one length to one destination.
+ * A routed batch interleaves its peers, so the batch is grouped first: on the GPU, from the d_peer and d_lens
+ * arrays that qgcm_chain_outgoing (or a resolve and qgcm_seal_batch) leave there.
+ *
+ * Packet i is sendable when d_peer[i] < max_keys of the context and d_lens[i] != 0: the skip rule of
+ * qgcm_udp_send_slots_to, and the accounting's rule for a peer at or above max_keys.  The plan of a batch:
+ *   order[0..m)   the sendable indices, sorted by peer ascending and by index ascending within a peer: arena
+ *                 order per link, so no flow is reordered
+ *   runs          the maximal stretches of order whose packets have one peer and one length L
+ *   cap(L)        1 when L > max_seg_len, else max(1, min(max_segs, max_bytes / L)) (integer division)
+ *   trains[0..t)  every run of r packets cut from its front into trains of cap(L) packets, the last holding
+ *                 the remainder: {first (an index into order), count, peer, seg_len (the common length)}.
+ *                 Trains follow order's order and tile [0, m) exactly
+ *   counts        {m, t}
+ * A shorter last segment, which the kernel interface would take, is not used.  Entries of order past m and of
+ * trains past t are unspecified.
+ *
+ * limits (NULL: all defaults): a zero field takes its default -- max_segs 64 (UDP_MAX_SEGMENTS of the oldest
+ * kernels with UDP_SEGMENT), max_seg_len 65507, max_bytes 65507; max_segs above 1024 (UIO_MAXIOV) or
+ * max_bytes above 65507: QGCM_E_ARG.  max_seg_len is the caller's path-MTU guard: a datagram longer than path
+ * MTU - 28 cannot be a segment (the kernel refuses the message), so it is planned as a train of one and goes
+ * out, fragmented, as it does today.
+ *
+ * qgcm_send_plan: device arrays, asynchronous on stream; d_order n uint32, d_trains n entries (16-B aligned),
+ * d_counts 2 uint32, d_work qgcm_send_plan_work(n) bytes of device memory, 256-B aligned, the call's own
+ * until it has run.  It keeps no state in the context beyond max_keys and needs no route table, so calls on
+ * several streams may run at once.  n == 0: QGCM_OK, nothing launched; n above QGCM_MAX_BATCH, a NULL or
+ * misaligned array, bad limits: QGCM_E_ARG, nothing launched.
+ * qgcm_send_plan_cpu: the same plan by the host (a counting sort per 8-bit digit of the peer, one pass for the
+ * trains), with max_keys in place of a context; allocates nothing (it borrows trains' storage while it
+ * sorts).  counts is written for n == 0 too.
+ * qgcm_send_plan_host: host arrays in and out, synchronous, serialised with the context's other routed host
+ * calls: copies lens and peer up (8 B a packet), plans on the context's routed stream in a work area the
+ * context owns and grows on demand, and copies counts, order[0..m) and trains[0..t) back.  Batches of fewer
+ * than QGCM_PLAN_DEVICE_MIN packets (environment, read at qgcm_create; 0: always the device, 4294967295:
+ * never; default 65536, the measured crossover of DESIGN.md 4.5) are planned by qgcm_send_plan_cpu's code
+ * instead; both paths write the same bytes. */
+typedef struct qgcm_train { uint32_t first, count, peer, seg_len; } qgcm_train;
+typedef struct qgcm_plan_limits { uint32_t max_segs, max_seg_len, max_bytes; } qgcm_plan_limits;
+uint64_t qgcm_send_plan_work(uint32_t n);
+int qgcm_send_plan(qgcm_ctx *ctx, uint32_t n, const uint32_t *d_lens, const uint32_t *d_peer,
+                   const qgcm_plan_limits *limits, uint32_t *d_order, qgcm_train *d_trains, uint32_t *d_counts,
+                   void *d_work, void *stream);
+int qgcm_send_plan_cpu(uint32_t n, const uint32_t *lens, const uint32_t *peer, uint32_t max_keys,
+                       const qgcm_plan_limits *limits, uint32_t *order, qgcm_train *trains, uint32_t counts[2]);
+int qgcm_send_plan_host(qgcm_ctx *ctx, uint32_t n, const uint32_t *h_lens, const uint32_t *h_peer,
+                        const qgcm_plan_limits *limits, uint32_t *h_order, qgcm_train *h_trains, uint32_t counts[2]);
+/* Sends a planned batch: one message per train, `count` iovecs (one per slot, nothing is copied), msg_name
+ * addrs[peer], and for count > 1 a UDP_SEGMENT control message of seg_len; in sendmmsg batches of at most
+ * 1024 messages over a bounded iovec pool.  lens are the batch's n datagram lengths, order / m and trains /
+ * n_trains the plan.  The whole plan is checked before anything is sent; any violation returns -1 with
+ * nothing sent: an order[j] >= n; a train with first + count > m, count outside [1, 1024] or peer >= n_addrs;
+ * a seg_len of 0, or above 65535 in a train of more than one (the segment size travels as 16 bits); a member
+ * whose lens differs from the train's seg_len or exceeds stride (a plan that does not match the lengths
+ * would move datagram boundaries).
+ * A segmented message that fails with EINVAL, EIO, EMSGSIZE, ENOPROTOOPT or EOPNOTSUPP (a kernel without
+ * UDP_SEGMENT, more segments than it takes, a segment above the path MTU) is sent again as `count` single
+ * datagrams and the call goes on; after ENOPROTOOPT or EOPNOTSUPP the rest of the call goes unsegmented
+ * without asking again (on such a host set QGCM_UDP_GSO=0 and save that one refusal per call).  A plain message that fails ends the call as qgcm_udp_send_slots_to ends:
+ * the number sent so far, or -1 if none; EINTR is retried.  QGCM_UDP_GSO=0 (environment, read at each call)
+ * sends every train unsegmented, in plan order.  Returns the number of datagrams sent.  stats (may be NULL):
+ * {messages sent, of them segmented, trains that fell back}. */
+int qgcm_udp_send_plan(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
+                       const uint32_t *order, uint32_t m, const qgcm_train *trains, uint32_t n_trains,
+                       const qgcm_peer_addr *addrs, uint32_t n_addrs, uint64_t stats[3]);
 
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19

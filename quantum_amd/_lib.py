@@ -41,6 +41,7 @@ EXPORTS = (
     "qgcm_route_seal_host", "qgcm_route_open_host", "qgcm_udp_send_slots_to",
     "qgcm_peer_plugins_set", "qgcm_peer_plugins_get", "qgcm_chain_outgoing", "qgcm_chain_incoming",
     "qgcm_route_account_bytes", "qgcm_route_chain_seal_host", "qgcm_route_chain_open_host",
+    "qgcm_send_plan_work", "qgcm_send_plan", "qgcm_send_plan_cpu", "qgcm_send_plan_host", "qgcm_udp_send_plan",
 )
 
 QGCM_OK = 0
@@ -93,6 +94,18 @@ class PeerAddr(C.Structure):
     """qgcm_peer_addr: {ip u32, port u16, pad u16}, network byte order."""
 
     _fields_ = [("ip", C.c_uint32), ("port", C.c_uint16), ("pad", C.c_uint16)]
+
+
+class Train(C.Structure):
+    """qgcm_train: {first (an index into the plan's order), count, peer, seg_len} -- 16 bytes."""
+
+    _fields_ = [("first", C.c_uint32), ("count", C.c_uint32), ("peer", C.c_uint32), ("seg_len", C.c_uint32)]
+
+
+class PlanLimits(C.Structure):
+    """qgcm_plan_limits: {max_segs, max_seg_len, max_bytes}; a zero field takes its default (64, 65507, 65507)."""
+
+    _fields_ = [("max_segs", C.c_uint32), ("max_seg_len", C.c_uint32), ("max_bytes", C.c_uint32)]
 
 
 _lib: C.CDLL | None = None
@@ -215,6 +228,13 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_route_account_bytes.argtypes = [vp, i32, u32, vp, vp, vp, vp]
         L.qgcm_route_chain_seal_host.argtypes = [vp, vp, u64, u32, vp, vp, u32, vp, vp]
         L.qgcm_route_chain_open_host.argtypes = [vp, vp, u64, u32, vp, u32, vp, vp]
+    if hasattr(L, "qgcm_send_plan"):  # (older builds loaded by the A/B tools lack the send plan)
+        L.qgcm_send_plan_work.argtypes = [u32]
+        L.qgcm_send_plan_work.restype = u64
+        L.qgcm_send_plan.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.qgcm_send_plan_cpu.argtypes = [u32, vp, vp, u32, vp, vp, vp, vp]
+        L.qgcm_send_plan_host.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
+        L.qgcm_udp_send_plan.argtypes = [C.c_int, vp, u64, u32, vp, vp, u32, vp, u32, vp, u32, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

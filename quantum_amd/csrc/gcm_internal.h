@@ -377,6 +377,16 @@ hipError_t launch_chain(ChainStage stage, bool fused, const ChainArgs &a, hipStr
 int run_snappy_gated(qgcm_ctx *ctx, bool compress, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
                      uint32_t max_in, uint32_t limit, uint32_t limit_b, uint8_t *d_status, const uint8_t *d_gate,
                      hipStream_t s);
+// The send plan of a routed batch (plan_kernels.hip; include/qgcm.h "send plan on routed batches"): `lim`
+// resolved by plan_limits_resolve (send_plan_core.h), work: send_plan_work_bytes(n) bytes, 256-B aligned.
+// Four kernels and the radix sort on s; n == 0 launches nothing.
+uint64_t send_plan_work_bytes(uint32_t n);
+hipError_t launch_send_plan(uint32_t n, uint32_t max_keys, const uint32_t *lens, const uint32_t *peer,
+                            const qgcm_plan_limits &lim, uint32_t *order, qgcm_train *trains, uint32_t *counts,
+                            void *work, uint64_t work_bytes, hipStream_t s);
+// qgcm_send_plan_host plans on the device from this many packets on (QGCM_PLAN_DEVICE_MIN at qgcm_create): the
+// measured crossover -- 181 against 186 us at 65536, 319 against 993 us at 262144
+constexpr uint32_t kPlanDeviceMin = 65536;
 // The context's route state (route.cpp): made by qgcm_create, freed by qgcm_destroy after the device is idle.
 struct RouteState;
 RouteState *route_state_create();

@@ -9,6 +9,7 @@
 // that is already freed.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 
 #include "../../include/qgcm.h"
 #include "gcm_internal.h"
+#include "send_plan_core.h"
 
 namespace qgcm {
 
@@ -40,9 +42,20 @@ struct RouteState {
     uint8_t *d_arena = nullptr, *d_side = nullptr;
     size_t arena_cap = 0, side_cap = 0;
     std::vector<uint8_t> h_stat;
+
+    // qgcm_send_plan_host: its device arrays and work area (under pipe_mu, on `stream`), and the batch size
+    // from which it plans on the device (QGCM_PLAN_DEVICE_MIN, read when the context is created)
+    uint8_t *d_plan = nullptr;
+    size_t plan_cap = 0;
+    uint32_t plan_device_min = kPlanDeviceMin;
 };
 
-RouteState *route_state_create() { return new RouteState(); }
+RouteState *route_state_create() {
+    RouteState *r = new RouteState();
+    if (const char *v = getenv("QGCM_PLAN_DEVICE_MIN"))
+        if (*v) r->plan_device_min = (uint32_t)std::min<unsigned long long>(strtoull(v, nullptr, 0), 0xffffffffull);
+    return r;
+}
 
 void route_state_destroy(RouteState *r) {
     if (!r) return;
@@ -51,6 +64,7 @@ void route_state_destroy(RouteState *r) {
     hipFree(r->d_plugins);
     hipFree(r->d_arena);
     hipFree(r->d_side);
+    hipFree(r->d_plan);
     if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
@@ -399,6 +413,76 @@ int qgcm_chain_incoming(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32
                         uint32_t *d_bytes, void *d_work, void *stream) {
     return run_chain(ctx, false, d_arena, stride, n, d_lens, d_peer, d_descs, plugins, nullptr, d_status, d_bytes, d_work,
                      (hipStream_t)stream);
+}
+
+uint64_t qgcm_send_plan_work(uint32_t n) { return n > QGCM_MAX_BATCH ? 0 : send_plan_work_bytes(n); }
+
+int qgcm_send_plan(qgcm_ctx *ctx, uint32_t n, const uint32_t *d_lens, const uint32_t *d_peer,
+                   const qgcm_plan_limits *limits, uint32_t *d_order, qgcm_train *d_trains, uint32_t *d_counts,
+                   void *d_work, void *stream) {
+    if (!ctx || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
+    if (n && (!d_lens || !d_peer || !d_order || !d_trains || !d_counts || !d_work)) return QGCM_E_ARG;
+    if (((uintptr_t)d_lens & 3) || ((uintptr_t)d_peer & 3) || ((uintptr_t)d_order & 3) || ((uintptr_t)d_trains & 15) ||
+        ((uintptr_t)d_counts & 3) || ((uintptr_t)d_work & 255))
+        return QGCM_E_ARG;
+    qgcm_plan_limits lim;
+    if (!plan_limits_resolve(limits, &lim)) return QGCM_E_ARG;
+    if (n == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    // the area is the size the caller was told (the one size query of the call)
+    return hip_rc(launch_send_plan(n, ctx_max_keys(ctx), d_lens, d_peer, lim, d_order, d_trains, d_counts, d_work,
+                                   send_plan_work_bytes(n), (hipStream_t)stream));
+}
+
+int qgcm_send_plan_cpu(uint32_t n, const uint32_t *lens, const uint32_t *peer, uint32_t max_keys,
+                       const qgcm_plan_limits *limits, uint32_t *order, qgcm_train *trains, uint32_t counts[2]) {
+    if (n > QGCM_MAX_BATCH || !counts || (n && (!lens || !peer || !order || !trains))) return QGCM_E_ARG;
+    qgcm_plan_limits lim;
+    if (!plan_limits_resolve(limits, &lim)) return QGCM_E_ARG;
+    send_plan_cpu(n, lens, peer, max_keys, lim, order, trains, counts);
+    return QGCM_OK;
+}
+
+int qgcm_send_plan_host(qgcm_ctx *ctx, uint32_t n, const uint32_t *h_lens, const uint32_t *h_peer,
+                        const qgcm_plan_limits *limits, uint32_t *h_order, qgcm_train *h_trains, uint32_t counts[2]) {
+    if (!ctx || n > QGCM_MAX_BATCH || !counts || (n && (!h_lens || !h_peer || !h_order || !h_trains)))
+        return QGCM_E_ARG;
+    qgcm_plan_limits lim;
+    if (!plan_limits_resolve(limits, &lim)) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    std::lock_guard<std::mutex> pg(r->pipe_mu);
+    if (n == 0 || n < r->plan_device_min) {
+        send_plan_cpu(n, h_lens, h_peer, ctx_max_keys(ctx), lim, h_order, h_trains, counts);
+        return QGCM_OK;
+    }
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
+        r->stream = nullptr;
+        return QGCM_E_HIP;
+    }
+    hipStream_t s = r->stream;
+    // trains (16-B aligned), lengths, peers, order, counts, then the work area (256-B aligned)
+    const size_t o_trains = 0, o_lens = o_trains + 16ull * n, o_peer = o_lens + 4ull * n, o_order = o_peer + 4ull * n,
+                 o_counts = o_order + 4ull * n, o_work = (o_counts + 8 + 255) & ~(size_t)255;
+    const uint64_t work_bytes = send_plan_work_bytes(n);
+    if (!grow(r->d_plan, r->plan_cap, o_work + (size_t)work_bytes)) return QGCM_E_NOMEM;
+    qgcm_train *d_trains = reinterpret_cast<qgcm_train *>(r->d_plan + o_trains);
+    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_plan + o_lens);
+    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_plan + o_peer);
+    uint32_t *d_order = reinterpret_cast<uint32_t *>(r->d_plan + o_order);
+    uint32_t *d_counts = reinterpret_cast<uint32_t *>(r->d_plan + o_counts);
+    // every way out waits for the stream: the next call reuses d_plan, and the caller its arrays
+    bool ok = hipMemcpyAsync(d_lens, h_lens, 4ull * n, hipMemcpyHostToDevice, s) == hipSuccess &&
+              hipMemcpyAsync(d_peer, h_peer, 4ull * n, hipMemcpyHostToDevice, s) == hipSuccess &&
+              launch_send_plan(n, ctx_max_keys(ctx), d_lens, d_peer, lim, d_order, d_trains, d_counts,
+                               r->d_plan + o_work, work_bytes, s) == hipSuccess &&
+              hipMemcpyAsync(counts, d_counts, 8, hipMemcpyDeviceToHost, s) == hipSuccess;
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
+    if (!ok || counts[0] > n || counts[1] > counts[0]) return QGCM_E_HIP;
+    ok = (!counts[0] || hipMemcpyAsync(h_order, d_order, 4ull * counts[0], hipMemcpyDeviceToHost, s) == hipSuccess) &&
+         (!counts[1] || hipMemcpyAsync(h_trains, d_trains, 16ull * counts[1], hipMemcpyDeviceToHost, s) == hipSuccess);
+    ok = hipStreamSynchronize(s) == hipSuccess && ok;
+    return ok ? QGCM_OK : QGCM_E_HIP;
 }
 
 int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]) {

@@ -10,7 +10,9 @@
 #include <arpa/inet.h>
 #include <errno.h>
 #include <netinet/in.h>
+#include <netinet/udp.h>
 #include <poll.h>
+#include <stdlib.h>
 #include <string.h>
 #include <sys/socket.h>
 #include <unistd.h>
@@ -19,6 +21,13 @@
 #include <vector>
 
 #include "../../include/qgcm.h"
+
+#ifndef UDP_SEGMENT
+#define UDP_SEGMENT 103  // linux/udp.h, Linux 4.18
+#endif
+#ifndef SOL_UDP
+#define SOL_UDP 17
+#endif
 
 namespace {
 
@@ -203,6 +212,150 @@ int qgcm_udp_send_slots_to(int fd, const uint8_t *arena, uint64_t stride, uint32
         }
     }
     return (int)sent;
+}
+
+// socket/udp.go:43-47 for a planned batch (qgcm_send_plan*): one message per train, its datagrams gathered
+// from their slots by one iovec each, cut apart again by the kernel's UDP_SEGMENT (one traversal of the UDP
+// stack per train in place of one per datagram).  The contract is in include/qgcm.h.
+int qgcm_udp_send_plan(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
+                       const uint32_t *order, uint32_t m, const qgcm_train *trains, uint32_t n_trains,
+                       const qgcm_peer_addr *addrs, uint32_t n_addrs, uint64_t stats[3]) {
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (fd < 0 || (n && (!arena || !lens)) || (m && !order) || (n_trains && !trains) || (n_addrs && !addrs)) return -1;
+    // the whole plan before the first byte leaves
+    for (uint32_t j = 0; j < m; ++j)
+        if (order[j] >= n) return -1;
+    for (uint32_t t = 0; t < n_trains; ++t) {
+        const qgcm_train &tr = trains[t];
+        if (tr.count < 1 || tr.count > kVlen || (uint64_t)tr.first + tr.count > m || tr.peer >= n_addrs) return -1;
+        // an empty datagram is never sendable; a segment size travels as 16 bits
+        if (tr.seg_len == 0 || tr.seg_len > stride || (tr.count > 1 && tr.seg_len > 65535u)) return -1;
+        for (uint32_t k = 0; k < tr.count; ++k)
+            if (lens[order[tr.first + k]] != tr.seg_len) return -1;
+    }
+    const char *gso_env = getenv("QGCM_UDP_GSO");
+    bool gso = !(gso_env && !strcmp(gso_env, "0"));
+
+    constexpr unsigned kIovPool = 4 * kVlen;  // a train takes at most kVlen of them
+    struct SegCtl {
+        alignas(cmsghdr) char buf[CMSG_SPACE(sizeof(uint16_t))];
+    };
+    std::vector<mmsghdr> msgs(kVlen);
+    std::vector<iovec> iov(kIovPool);
+    std::vector<sockaddr_in> dst(kVlen);
+    std::vector<SegCtl> ctl(kVlen);
+    std::vector<uint32_t> msg_train(kVlen);  // the train of each queued message
+    uint64_t sent = 0, n_msgs = 0, n_seg = 0, n_fell = 0;
+    auto finish = [&](bool failed) {
+        if (stats) {
+            stats[0] = n_msgs;
+            stats[1] = n_seg;
+            stats[2] = n_fell;
+        }
+        return failed && sent == 0 ? -1 : (int)sent;
+    };
+    auto slot_iov = [&](uint32_t pos, uint32_t len) {
+        return iovec{const_cast<uint8_t *>(arena) + (uint64_t)order[pos] * stride, (size_t)len};
+    };
+    auto set_dst = [&](sockaddr_in *d, uint32_t peer) {
+        memset(d, 0, sizeof *d);
+        d->sin_family = AF_INET;
+        d->sin_addr.s_addr = addrs[peer].ip;  // network byte order already
+        d->sin_port = addrs[peer].port;
+    };
+    // a train as `count` plain datagrams (count <= kVlen), through buffers of its own: the segmented
+    // messages queued behind a train that fell back keep theirs; false: a send failed
+    std::vector<mmsghdr> one_msgs;
+    std::vector<iovec> one_iov;
+    sockaddr_in one_dst;
+    auto send_singles = [&](const qgcm_train &tr) {
+        one_msgs.resize(kVlen);
+        one_iov.resize(kVlen);
+        set_dst(&one_dst, tr.peer);
+        for (uint32_t i = 0; i < tr.count; ++i) {
+            one_iov[i] = slot_iov(tr.first + i, tr.seg_len);
+            one_msgs[i] = mmsghdr{};
+            one_msgs[i].msg_hdr.msg_name = &one_dst;
+            one_msgs[i].msg_hdr.msg_namelen = sizeof one_dst;
+            one_msgs[i].msg_hdr.msg_iov = &one_iov[i];
+            one_msgs[i].msg_hdr.msg_iovlen = 1;
+        }
+        for (uint32_t done = 0; done < tr.count;) {
+            const int r = sendmmsg(fd, one_msgs.data() + done, tr.count - done, 0);
+            if (r < 0) {
+                if (errno == EINTR) continue;
+                return false;
+            }
+            done += (uint32_t)r;
+            sent += (uint64_t)r;
+            n_msgs += (uint64_t)r;
+        }
+        return true;
+    };
+
+    uint32_t next = 0;  // the next train to queue
+    while (next < n_trains) {
+        unsigned k = 0, used = 0;  // messages and iovecs queued; an empty queue takes any train
+        for (; next < n_trains; ++next) {
+            const qgcm_train &tr = trains[next];
+            // a segmented train is one message of `count` iovecs; a train of one, and every train under
+            // QGCM_UDP_GSO=0, is `count` plain messages
+            const bool seg = gso && tr.count > 1;
+            const unsigned n_new = seg ? 1u : tr.count;
+            if (k + n_new > kVlen || used + tr.count > kIovPool) break;
+            for (uint32_t i = 0; i < tr.count; ++i) iov[used + i] = slot_iov(tr.first + i, tr.seg_len);
+            for (unsigned i = 0; i < n_new; ++i, ++k) {
+                set_dst(&dst[k], tr.peer);
+                msgs[k] = mmsghdr{};
+                msghdr &h = msgs[k].msg_hdr;
+                h.msg_name = &dst[k];
+                h.msg_namelen = sizeof dst[k];
+                h.msg_iov = &iov[used + i];
+                h.msg_iovlen = seg ? tr.count : 1;
+                if (seg) {
+                    memset(ctl[k].buf, 0, sizeof ctl[k].buf);
+                    h.msg_control = ctl[k].buf;
+                    h.msg_controllen = sizeof ctl[k].buf;
+                    cmsghdr *cm = CMSG_FIRSTHDR(&h);
+                    cm->cmsg_level = SOL_UDP;
+                    cm->cmsg_type = UDP_SEGMENT;
+                    cm->cmsg_len = CMSG_LEN(sizeof(uint16_t));
+                    const uint16_t seg_len = (uint16_t)tr.seg_len;
+                    memcpy(CMSG_DATA(cm), &seg_len, sizeof seg_len);
+                }
+                msg_train[k] = next;
+            }
+            used += tr.count;
+        }
+        for (unsigned done = 0; done < k;) {
+            const int r = sendmmsg(fd, msgs.data() + done, k - done, 0);
+            if (r >= 0) {
+                for (int i = 0; i < r; ++i) {  // a message carries one datagram per iovec
+                    sent += msgs[done + i].msg_hdr.msg_iovlen;
+                    n_seg += msgs[done + i].msg_hdr.msg_iovlen > 1;
+                }
+                n_msgs += (uint64_t)r;
+                done += (unsigned)r;
+                continue;
+            }
+            if (errno == EINTR) continue;
+            // msgs[done] is the one that failed
+            const bool unsupported = errno == ENOPROTOOPT || errno == EOPNOTSUPP;
+            const bool refused = unsupported || errno == EINVAL || errno == EIO || errno == EMSGSIZE;
+            if (msgs[done].msg_hdr.msg_iovlen == 1 || !refused) return finish(true);
+            ++n_fell;
+            if (!send_singles(trains[msg_train[done]])) return finish(true);
+            ++done;
+            if (unsupported) {
+                // this socket takes no UDP_SEGMENT at all: the trains queued behind this one, and the rest
+                // of the call, go unsegmented without asking again
+                gso = false;
+                if (done < k) next = msg_train[done];
+                break;
+            }
+        }
+    }
+    return finish(false);
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@ stream handles only.
 
 main.go:41-51              the node's plugins in order  -> Router(plugins=...), chain_outgoing / chain_incoming
 plugin/compression.go:31-33, plugin/encryption.go:17-19  the per-peer gate -> peer_plugins_set, plugin_flags
+socket/udp.go:43-47        Write, grouped per peer into UDP_SEGMENT trains -> send_plan, send_plan_host,
+                           send_plan_cpu, udp_send_plan
 """
 from __future__ import annotations
 
@@ -262,6 +264,71 @@ def peer_addrs(addrs) -> C.Array:
         arr[i].ip = struct.unpack("=I", socket.inet_aton(ip))[0]  # the address bytes in memory order, as s_addr
         arr[i].port = socket.htons(port)
     return arr
+
+
+def plan_limits(max_segs: int = 0, max_seg_len: int = 0, max_bytes: int = 0) -> _lib.PlanLimits:
+    """qgcm_plan_limits: a zero field takes its default (64 segments, 65507 bytes a segment, 65507 bytes a
+    train); max_seg_len is the path MTU - 28."""
+    return _lib.PlanLimits(max_segs, max_seg_len, max_bytes)
+
+
+def _limits_ptr(limits):
+    return None if limits is None else C.addressof(limits)
+
+
+def send_plan_work(n: int, device="cuda"):
+    """A work area for a send_plan call of n packets (qgcm_send_plan_work(n) bytes; torch allocations are
+    512-B aligned)."""
+    import torch
+
+    return torch.empty(max(256, int(_lib.lib().qgcm_send_plan_work(n))), dtype=torch.uint8, device=device)
+
+
+def send_plan(ctx, n: int, lens, peer, order, trains, counts, work, limits=None, stream=None) -> None:
+    """qgcm_send_plan after chain_outgoing (or a seal) on the same stream: `lens` / `peer` / `order` int32 (n),
+    `trains` int32 (4 n: first, count, peer, seg_len per train), `counts` int32 (2: m, t), `work` from
+    send_plan_work(n); `limits` from plan_limits() or None."""
+    _lib.check(_lib.lib().qgcm_send_plan(ctx.handle, n, _ptr(lens), _ptr(peer), _limits_ptr(limits), _ptr(order),
+                                         _ptr(trains), _ptr(counts), _ptr(work), _stream_handle(stream)),
+               "qgcm_send_plan")
+
+
+def _plan_arrays(n: int):
+    import numpy as np
+
+    return np.zeros(max(1, n), np.uint32), np.zeros((max(1, n), 4), np.uint32), np.zeros(2, np.uint32)
+
+
+def send_plan_cpu(lens, peer, max_keys: int, limits=None):
+    """qgcm_send_plan_cpu over numpy uint32 arrays -> (order[:m], trains[:t]): `trains` a (t, 4) uint32 array of
+    first, count, peer, seg_len."""
+    n = len(lens)
+    order, trains, counts = _plan_arrays(n)
+    _lib.check(_lib.lib().qgcm_send_plan_cpu(n, lens.ctypes.data, peer.ctypes.data, max_keys, _limits_ptr(limits),
+                                             order.ctypes.data, trains.ctypes.data, counts.ctypes.data),
+               "qgcm_send_plan_cpu")
+    return order[:counts[0]], trains[:counts[1]]
+
+
+def send_plan_host(ctx, lens, peer, limits=None):
+    """qgcm_send_plan_host: the plan of what route_chain_seal_host (or route_seal_host) left in `lens` and `peer`
+    (numpy uint32) -> (order[:m], trains[:t]) as send_plan_cpu."""
+    n = len(lens)
+    order, trains, counts = _plan_arrays(n)
+    _lib.check(_lib.lib().qgcm_send_plan_host(ctx.handle, n, lens.ctypes.data, peer.ctypes.data, _limits_ptr(limits),
+                                              order.ctypes.data, trains.ctypes.data, counts.ctypes.data),
+               "qgcm_send_plan_host")
+    return order[:counts[0]], trains[:counts[1]]
+
+
+def udp_send_plan(fd: int, arena_ptr: int, stride: int, n: int, lens, order, trains, addrs: C.Array, n_addrs: int,
+                  stats=None) -> int:
+    """qgcm_udp_send_plan: one message per train (UDP_SEGMENT for count > 1) to addrs[peer]; `order` numpy
+    uint32 (m), `trains` numpy uint32 (t, 4), `stats` a numpy uint64 array of 3 or None.  Returns the number of
+    datagrams sent or -1."""
+    return _lib.lib().qgcm_udp_send_plan(fd, arena_ptr, stride, n, lens.ctypes.data, order.ctypes.data, len(order),
+                                         trains.ctypes.data, len(trains), C.addressof(addrs), n_addrs,
+                                         None if stats is None else stats.ctypes.data)
 
 
 def udp_send_slots_to(fd: int, arena_ptr: int, stride: int, n: int, lens, peer, addrs: C.Array, n_addrs: int) -> int:
