@@ -22,6 +22,9 @@
  *                            qgcm_route_account_bytes, qgcm_route_chain_seal_host / qgcm_route_chain_open_host
  *   socket/udp.go:44-47 Write(payload, mapping)               -> qgcm_udp_send_slots_to, or grouped per peer:
  *                                                                qgcm_send_plan + qgcm_udp_send_plan
+ *   socket/udp.go:35-41 Read() for a batch                    -> qgcm_udp_recv_slots, or coalesced (UDP_GRO):
+ *                                                                qgcm_udp_recv_gro + qgcm_gro_unpack /
+ *                                                                qgcm_route_chain_open_gro_host
  *
  * Error convention follows the reference's own cgo layer (crypto/dtls.go:37-40, dtls.h:43-48):
  * constructors return NULL and fill a caller-supplied error buffer; everything else returns
@@ -665,6 +668,75 @@ int qgcm_send_plan_host(qgcm_ctx *ctx, uint32_t n, const uint32_t *h_lens, const
 int qgcm_udp_send_plan(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
                        const uint32_t *order, uint32_t m, const qgcm_train *trains, uint32_t n_trains,
                        const qgcm_peer_addr *addrs, uint32_t n_addrs, uint64_t stats[3]);
+
+/* ---- coalesced receive on routed batches: UDP_GRO buffers unpacked into slots ---- */
+/* With the UDP_GRO socket option one recvmsg returns a whole train of equal-length datagrams of one sender --
+ * what qgcm_udp_send_plan puts on the wire -- as one buffer, with the segment size in a control message.  The
+ * buffers are received back to back into a packed byte area, cross to the device at their own size, and a
+ * kernel scatters their datagrams into the slots that resolve, chain and accounting take.
+ *
+ * qgcm_gro_buf describes one received buffer inside the packed area: off its byte offset (any alignment), len
+ * the bytes received (0 .. 65535), seg_len the value of the UDP_GRO control message or 0 when there was none,
+ * first the slot of its first datagram.  The buffer holds `count` datagrams: 1 when seg_len == 0 or seg_len >=
+ * len (a lone datagram, one of length 0 included), else ceil(len / seg_len).  Datagram k is packed[off +
+ * k * seg_len ..) of length L = min(seg_len, len - k * seg_len) (len when count is 1) and belongs to slot
+ * first + k.  The unpack sets d_lens[first + k] = L and bytes [0, min(L, stride)) of that slot to the
+ * datagram's; every other byte of the arena and every other length stays as it was (slot tails, slots no
+ * buffer names).  A datagram longer than stride keeps its true length, which qgcm_resolve_incoming treats as
+ * a miss.  A buffer with off + len > packed_len or first + count > n is skipped whole: nothing is written for
+ * it.
+ *
+ * qgcm_udp_gro sets the socket option (on: 1 / 0); returns 0 or -errno.
+ * qgcm_udp_recv_gro waits up to timeout_ms (-1: forever) for the first datagram as qgcm_udp_recv_slots does,
+ * then takes what is queued with MSG_DONTWAIT, each recvmsg straight into the packed area at the fill position
+ * rounded up to 16 B (every off is a multiple of 16), and writes one entry per buffer, `first` included.  It
+ * stops before a receive when fewer than 65536 bytes of room are left (a coalesced buffer is never
+ * truncated), when max_bufs entries are written, or when fewer than QGCM_GRO_SEGS slots of max_n are left
+ * (the kernel's cap per buffer); what it did not take stays queued for the next call.  Returns the number of
+ * datagrams n (the slots the table names), 0 on timeout, or -1 (also for a NULL array, and for a packed_cap,
+ * max_bufs or max_n that allows no receive at all).  out (may be NULL): {buffers, bytes of the packed area
+ * used = the end of the last buffer, datagrams cut}.  A buffer with more datagrams than slots are left is cut
+ * to the ones that fit and the rest are counted in out[2]; no current kernel produces one.  Works with the
+ * option off and on a host that does not coalesce: every buffer is then one datagram.
+ *
+ * qgcm_gro_unpack: device arrays, asynchronous on stream, no context state (calls on several streams may run
+ * at once).  d_packed 16-B aligned and its allocation rounded up to 16 B: the kernel may read up to the 16-B
+ * boundary behind packed_len, never further.  d_bufs 16-B aligned, d_lens 4-B aligned; stride a nonzero
+ * multiple of 4 and d_arena 4-B aligned (a stride that is a multiple of 16 under a 16-B-aligned arena takes
+ * the 16-byte path).  The `first` values ascend, as qgcm_udp_recv_gro writes them (each slot finds its buffer
+ * by a binary search over them); a table in which they do not is memory-safe, and which of its slots are
+ * written is unspecified.  n == 0 or n_bufs == 0: QGCM_OK, nothing launched.  n > QGCM_MAX_BATCH, n_bufs > n,
+ * a bad stride, a NULL or misaligned pointer: QGCM_E_ARG.
+ * qgcm_gro_unpack_cpu: the same for host arrays (no alignment asked), by the host, so that a worker can use
+ * the coalesced receive with qgcm_route_open_host.  It checks the table first: each `first` is the exclusive
+ * prefix sum of the counts before it and the counts total n; if not, QGCM_E_ARG and nothing is written.
+ *
+ * qgcm_route_open_gro_host / qgcm_route_chain_open_gro_host: qgcm_route_open_host /
+ * qgcm_route_chain_open_host with the copy-in replaced.  The table is checked as in qgcm_gro_unpack_cpu
+ * (QGCM_E_ARG, nothing launched).  The batch is cut into chunks at buffer boundaries under the packet and
+ * byte limits of those calls (a buffer with more datagrams than a chunk holds is a chunk of its own); per
+ * chunk only the chunk's packed bytes and table entries are copied up, unpacked into the context's device
+ * arena, then resolved, opened or chained, accounted and copied back as in those calls, serialised on the
+ * context's routed stream like them.  h_lens is output only.  h_peer, h_status, h_lens, the return value
+ * and the Rx counters are what the existing call gives for the arena and lengths that qgcm_gro_unpack_cpu
+ * makes of the same input (a buffer past packed_len counts as datagrams of length 0); delivered packets are
+ * equal over Raw[:4 + h_lens[i]], dropped ones over Raw[:datagram length].  The slot bytes behind that are
+ * unspecified: they come from the context's device arena, not from h_arena. */
+#define QGCM_GRO_SEGS 64u
+typedef struct qgcm_gro_buf { uint32_t off, len, seg_len, first; } qgcm_gro_buf;
+int qgcm_udp_gro(int fd, int on);
+int qgcm_udp_recv_gro(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_gro_buf *bufs, uint32_t max_bufs,
+                      uint32_t max_n, int timeout_ms, uint64_t out[3]);
+int qgcm_gro_unpack(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gro_buf *d_bufs,
+                    uint32_t n_bufs, uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens, void *stream);
+int qgcm_gro_unpack_cpu(const uint8_t *packed, uint64_t packed_len, const qgcm_gro_buf *bufs, uint32_t n_bufs,
+                        uint32_t n, uint8_t *arena, uint64_t stride, uint32_t *lens);
+int qgcm_route_open_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gro_buf *bufs,
+                             uint32_t n_bufs, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                             uint32_t *h_peer, uint8_t *h_status);
+int qgcm_route_chain_open_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
+                                   const qgcm_gro_buf *bufs, uint32_t n_bufs, uint8_t *h_arena, uint64_t stride,
+                                   uint32_t n, uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status);
 
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19

@@ -42,6 +42,8 @@ EXPORTS = (
     "qgcm_peer_plugins_set", "qgcm_peer_plugins_get", "qgcm_chain_outgoing", "qgcm_chain_incoming",
     "qgcm_route_account_bytes", "qgcm_route_chain_seal_host", "qgcm_route_chain_open_host",
     "qgcm_send_plan_work", "qgcm_send_plan", "qgcm_send_plan_cpu", "qgcm_send_plan_host", "qgcm_udp_send_plan",
+    "qgcm_udp_gro", "qgcm_udp_recv_gro", "qgcm_gro_unpack", "qgcm_gro_unpack_cpu",
+    "qgcm_route_open_gro_host", "qgcm_route_chain_open_gro_host",
 )
 
 QGCM_OK = 0
@@ -54,6 +56,7 @@ OVERHEAD = 28
 NO_PEER = 0xFFFFFFFF  # QGCM_NO_PEER: a packet no route resolves, an empty route-table entry
 TX, RX = 0, 1  # QGCM_TX / QGCM_RX
 PLUGIN_COMPRESSION, PLUGIN_ENCRYPTION = 1, 2  # QGCM_PLUGIN_*: per-peer plugin flags, the node's own mask
+GRO_SEGS = 64  # QGCM_GRO_SEGS: the most datagrams the kernel coalesces into one received buffer
 
 
 def chain_work(n: int) -> int:
@@ -106,6 +109,13 @@ class PlanLimits(C.Structure):
     """qgcm_plan_limits: {max_segs, max_seg_len, max_bytes}; a zero field takes its default (64, 65507, 65507)."""
 
     _fields_ = [("max_segs", C.c_uint32), ("max_seg_len", C.c_uint32), ("max_bytes", C.c_uint32)]
+
+
+class GroBuf(C.Structure):
+    """qgcm_gro_buf: {off, len, seg_len (0: no UDP_GRO control message), first (slot of the first datagram)} --
+    16 bytes."""
+
+    _fields_ = [("off", C.c_uint32), ("len", C.c_uint32), ("seg_len", C.c_uint32), ("first", C.c_uint32)]
 
 
 _lib: C.CDLL | None = None
@@ -235,6 +245,13 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_send_plan_cpu.argtypes = [u32, vp, vp, u32, vp, vp, vp, vp]
         L.qgcm_send_plan_host.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         L.qgcm_udp_send_plan.argtypes = [C.c_int, vp, u64, u32, vp, vp, u32, vp, u32, vp, u32, vp]
+    if hasattr(L, "qgcm_gro_unpack"):  # (older builds loaded by the A/B tools lack the coalesced receive)
+        L.qgcm_udp_gro.argtypes = [C.c_int, C.c_int]
+        L.qgcm_udp_recv_gro.argtypes = [C.c_int, vp, u64, vp, u32, u32, C.c_int, vp]
+        L.qgcm_gro_unpack.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, vp]
+        L.qgcm_gro_unpack_cpu.argtypes = [vp, u64, vp, u32, u32, vp, u64, vp]
+        L.qgcm_route_open_gro_host.argtypes = [vp, vp, u64, vp, u32, vp, u64, u32, vp, vp, vp]
+        L.qgcm_route_chain_open_gro_host.argtypes = [vp, vp, u64, vp, u32, vp, u64, u32, vp, u32, vp, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

@@ -18,6 +18,7 @@
 
 #include "../../include/qgcm.h"
 #include "gcm_internal.h"
+#include "gro_core.h"
 #include "send_plan_core.h"
 
 namespace qgcm {
@@ -48,6 +49,12 @@ struct RouteState {
     uint8_t *d_plan = nullptr;
     size_t plan_cap = 0;
     uint32_t plan_device_min = kPlanDeviceMin;
+
+    // the coalesced-receive pipelines: a chunk's table and packed bytes on the device, the rebased table on
+    // the host (under pipe_mu, on `stream`)
+    uint8_t *d_gro = nullptr;
+    size_t gro_cap = 0;
+    std::vector<qgcm_gro_buf> h_gro;
 };
 
 RouteState *route_state_create() {
@@ -65,6 +72,7 @@ void route_state_destroy(RouteState *r) {
     hipFree(r->d_arena);
     hipFree(r->d_side);
     hipFree(r->d_plan);
+    hipFree(r->d_gro);
     if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
@@ -296,6 +304,121 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
     return dropped;
 }
 
+// Incoming.pipeline for a batch that arrived as coalesced buffers (qgcm_udp_recv_gro): run_route_host's open
+// side with the copy-in replaced.  Chunks end at buffer boundaries; per chunk the packed bytes its buffers
+// span and their table entries (rebased to the span and to the chunk's first slot) go up, gro_unpack_kernel
+// scatters them into the device arena, and resolve, open or chain, accounting and the copy back follow as in
+// run_route_host.  The lengths start as zeros on the device, so the slots of a buffer the kernel skips (one
+// past packed_len) are datagrams of length 0.
+int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gro_buf *bufs,
+                       uint32_t n_bufs, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens, uint32_t *h_peer,
+                       uint8_t *h_status, bool chain, uint32_t plugins) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || n > QGCM_MAX_BATCH || n_bufs > n) return QGCM_E_ARG;
+    if (n && (!h_packed || !bufs || !h_arena || !h_lens || !h_peer || stride == 0)) return QGCM_E_ARG;
+    if (chain && (plugins & ~kAllPlugins)) return QGCM_E_ARG;
+    if (!gro_table_ok(bufs, n_bufs, n)) return QGCM_E_ARG;
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+    }
+    if (n == 0) return 0;
+    std::lock_guard<std::mutex> pg(r->pipe_mu);
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
+        r->stream = nullptr;
+        return QGCM_E_HIP;
+    }
+    hipStream_t s = r->stream;
+    const uint32_t limit = (uint32_t)std::min<uint64_t>(kRouteChunk, std::max<uint64_t>(1, kRouteChunkBytes / stride));
+    // the chunks: buffers [b0, b1), slots [c0, c0 + cn), packed bytes [lo, hi) (lo on a 16-B boundary)
+    struct Chunk {
+        uint32_t b0, b1, c0, cn;
+        uint64_t lo, hi;
+    };
+    std::vector<Chunk> chunks;
+    uint32_t max_cn = 0, max_nb = 0;
+    uint64_t max_span = 0;
+    for (uint32_t b = 0; b < n_bufs;) {
+        Chunk c{b, b, bufs[b].first, 0, UINT64_MAX, 0};
+        for (; b < n_bufs; ++b) {
+            const uint32_t count = (uint32_t)gro_count(bufs[b].len, bufs[b].seg_len);  // at most n: the table is checked
+            if (c.cn && (uint64_t)c.cn + count > limit) break;
+            c.cn += count;
+            if ((uint64_t)bufs[b].off + bufs[b].len > packed_len) continue;  // skipped by the kernel: none of its bytes go up
+            c.lo = std::min<uint64_t>(c.lo, bufs[b].off & ~15u);
+            c.hi = std::max<uint64_t>(c.hi, (uint64_t)bufs[b].off + bufs[b].len);
+        }
+        c.b1 = b;
+        if (c.lo > c.hi) c.lo = c.hi = 0;
+        max_cn = std::max(max_cn, c.cn);
+        max_nb = std::max(max_nb, c.b1 - c.b0);
+        max_span = std::max(max_span, c.hi - c.lo);
+        chunks.push_back(c);
+    }
+    // side buffer of a chunk as in run_route_host (no nonces); the table (16-B aligned) and the packed bytes
+    // (16-B aligned, rounded up to 16 B) in a staging area of their own
+    const size_t o_desc = 0, o_lens = o_desc + 16ull * max_cn, o_peer = o_lens + 4ull * max_cn, o_stat = o_peer + 4ull * max_cn,
+                 o_bytes = (o_stat + max_cn + 15) & ~(size_t)15, o_work = o_bytes + 4 * (size_t)chain_work_lanes(max_cn),
+                 side = chain ? o_work + QGCM_CHAIN_WORK(max_cn) : o_stat + max_cn;
+    const size_t o_packed = 16ull * max_nb, gro = o_packed + (size_t)((max_span + 15) & ~(uint64_t)15);
+    if (!grow(r->d_arena, r->arena_cap, (size_t)max_cn * stride) || !grow(r->d_side, r->side_cap, side) ||
+        !grow(r->d_gro, r->gro_cap, std::max<size_t>(gro, 16)))
+        return QGCM_E_NOMEM;
+    r->h_stat.resize(max_cn);
+    r->h_gro.resize(max_nb);
+    qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
+    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
+    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
+    uint8_t *d_stat = r->d_side + o_stat;
+    uint32_t *d_bytes = reinterpret_cast<uint32_t *>(r->d_side + o_bytes);
+    qgcm_gro_buf *d_bufs = reinterpret_cast<qgcm_gro_buf *>(r->d_gro);
+    uint8_t *d_packed = r->d_gro + o_packed;
+    int dropped = 0;
+    for (const Chunk &c : chunks) {
+        const uint32_t nb = c.b1 - c.b0, cn = c.cn, c0 = c.c0;
+        for (uint32_t j = 0; j < nb; ++j) {
+            const qgcm_gro_buf &b = bufs[c.b0 + j];
+            const bool past = (uint64_t)b.off + b.len > packed_len;
+            // a buffer past packed_len stays one the kernel skips: its one entry keeps the search over `first` whole
+            r->h_gro[j] = past ? qgcm_gro_buf{0xffffffffu, 1, 0, b.first - c0}
+                               : qgcm_gro_buf{(uint32_t)(b.off - c.lo), b.len, b.seg_len, b.first - c0};
+        }
+        uint8_t *h = h_arena + (uint64_t)c0 * stride;
+        if (hipMemsetAsync(d_lens, 0, 4ull * cn, s) != hipSuccess ||
+            (c.hi > c.lo && hipMemcpyAsync(d_packed, h_packed + c.lo, (size_t)(c.hi - c.lo), hipMemcpyHostToDevice, s) != hipSuccess) ||
+            hipMemcpyAsync(d_bufs, r->h_gro.data(), 16ull * nb, hipMemcpyHostToDevice, s) != hipSuccess)
+            return QGCM_E_HIP;
+        int rc = hip_rc(launch_gro_unpack(d_packed, c.hi - c.lo, d_bufs, nb, cn, r->d_arena, stride, d_lens, s));
+        if (rc == QGCM_OK) rc = resolve(ctx, false, r->d_arena, stride, cn, d_lens, d_peer, d_descs, s);
+        if (rc == QGCM_OK && chain) {
+            rc = run_chain(ctx, false, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, nullptr, d_stat, d_bytes,
+                           r->d_side + o_work, s);
+            if (rc == QGCM_OK) rc = account(ctx, QGCM_RX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
+        } else if (rc == QGCM_OK) {
+            rc = qgcm_open_batch(ctx, r->d_arena, d_descs, cn, 4, d_stat, s);
+            if (rc == QGCM_OK) rc = qgcm_route_account(ctx, QGCM_RX, cn, d_peer, d_descs, d_stat, s);
+        }
+        // the lengths come back in both forms: the chain's are final, the open's are the datagrams'
+        if (rc == QGCM_OK &&
+            (hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess))
+            rc = QGCM_E_HIP;
+        if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
+        if (rc != QGCM_OK) return rc;
+        for (uint32_t i = 0; i < cn; ++i) {
+            const bool ok = r->h_stat[i] == 1;
+            if (!chain) h_lens[c0 + i] = ok ? h_lens[c0 + i] - 4 - QGCM_OVERHEAD : 0;
+            if (h_status) h_status[c0 + i] = ok ? 1 : 0;
+            dropped += !ok;
+        }
+    }
+    return dropped;
+}
+
 }  // namespace
 
 extern "C" {
@@ -483,6 +606,39 @@ int qgcm_send_plan_host(qgcm_ctx *ctx, uint32_t n, const uint32_t *h_lens, const
          (!counts[1] || hipMemcpyAsync(h_trains, d_trains, 16ull * counts[1], hipMemcpyDeviceToHost, s) == hipSuccess);
     ok = hipStreamSynchronize(s) == hipSuccess && ok;
     return ok ? QGCM_OK : QGCM_E_HIP;
+}
+
+int qgcm_gro_unpack(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gro_buf *d_bufs,
+                    uint32_t n_bufs, uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens, void *stream) {
+    if (!ctx || n > QGCM_MAX_BATCH || n_bufs > n || (stride & 3)) return QGCM_E_ARG;
+    if (n_bufs && (!d_packed || !d_bufs || !d_arena || !d_lens || stride == 0)) return QGCM_E_ARG;
+    if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_bufs & 15) || ((uintptr_t)d_arena & 3) || ((uintptr_t)d_lens & 3))
+        return QGCM_E_ARG;
+    if (n == 0 || n_bufs == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    return hip_rc(launch_gro_unpack(d_packed, packed_len, d_bufs, n_bufs, n, d_arena, stride, d_lens, (hipStream_t)stream));
+}
+
+int qgcm_gro_unpack_cpu(const uint8_t *packed, uint64_t packed_len, const qgcm_gro_buf *bufs, uint32_t n_bufs,
+                        uint32_t n, uint8_t *arena, uint64_t stride, uint32_t *lens) {
+    if (n > QGCM_MAX_BATCH || n_bufs > n || (stride & 3)) return QGCM_E_ARG;
+    if (n && (!packed || !bufs || !arena || !lens || stride == 0)) return QGCM_E_ARG;
+    if (!gro_table_ok(bufs, n_bufs, n)) return QGCM_E_ARG;
+    gro_unpack_cpu(packed, packed_len, bufs, n_bufs, n, arena, stride, lens);
+    return QGCM_OK;
+}
+
+int qgcm_route_open_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gro_buf *bufs,
+                             uint32_t n_bufs, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
+                             uint32_t *h_peer, uint8_t *h_status) {
+    return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, h_arena, stride, n, h_lens, h_peer, h_status, false, 0);
+}
+
+int qgcm_route_chain_open_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
+                                   const qgcm_gro_buf *bufs, uint32_t n_bufs, uint8_t *h_arena, uint64_t stride,
+                                   uint32_t n, uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status) {
+    return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, h_arena, stride, n, h_lens, h_peer, h_status, true,
+                              plugins);
 }
 
 int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]) {

@@ -21,9 +21,13 @@
 #include <vector>
 
 #include "../../include/qgcm.h"
+#include "gro_core.h"
 
 #ifndef UDP_SEGMENT
 #define UDP_SEGMENT 103  // linux/udp.h, Linux 4.18
+#endif
+#ifndef UDP_GRO
+#define UDP_GRO 104  // linux/udp.h, Linux 5.0
 #endif
 #ifndef SOL_UDP
 #define SOL_UDP 17
@@ -32,6 +36,7 @@
 namespace {
 
 constexpr unsigned kVlen = 1024;  // UIO_MAXIOV: most messages one recvmmsg/sendmmsg call takes
+constexpr uint64_t kGroRoom = 65536;  // room one coalesced receive needs: no buffer is longer than 65535 bytes
 
 bool make_addr(const char *ip, int port, sockaddr_in *a) {
     memset(a, 0, sizeof *a);
@@ -356,6 +361,78 @@ int qgcm_udp_send_plan(int fd, const uint8_t *arena, uint64_t stride, uint32_t n
         }
     }
     return finish(false);
+}
+
+// socket/udp.go:49-70 plus the UDP_GRO option: the kernel then hands a train of equal-length datagrams of one
+// sender back as one buffer (qgcm_udp_recv_gro).
+int qgcm_udp_gro(int fd, int on) {
+    const int v = on ? 1 : 0;
+    return setsockopt(fd, SOL_UDP, UDP_GRO, &v, sizeof v) == 0 ? 0 : -errno;
+}
+
+// socket/udp.go:35-41 for coalesced buffers: one recvmsg per buffer, straight into the packed area, one
+// table entry each.  The contract is in include/qgcm.h.
+int qgcm_udp_recv_gro(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_gro_buf *bufs, uint32_t max_bufs,
+                      uint32_t max_n, int timeout_ms, uint64_t out[3]) {
+    if (out) out[0] = out[1] = out[2] = 0;
+    if (fd < 0 || !packed || !bufs || packed_cap < kGroRoom || max_bufs == 0 || max_n < QGCM_GRO_SEGS) return -1;
+    pollfd p{fd, POLLIN, 0};
+    int pr;
+    do {
+        pr = poll(&p, 1, timeout_ms);
+    } while (pr < 0 && errno == EINTR);
+    if (pr < 0) return -1;
+    if (pr == 0) return 0;
+    max_n = std::min<uint32_t>(max_n, 0x7fffffffu);       // the count is returned as an int
+    packed_cap = std::min<uint64_t>(packed_cap, 1ull << 32);  // offsets are 32-bit
+    uint64_t fill = 0, used = 0, cut = 0;
+    uint32_t nb = 0, n = 0;
+    bool failed = false;
+    while (fill + kGroRoom <= packed_cap && nb < max_bufs && max_n - n >= QGCM_GRO_SEGS) {
+        alignas(cmsghdr) char ctl[CMSG_SPACE(sizeof(int))];
+        iovec iov{packed + fill, (size_t)kGroRoom};
+        msghdr h{};
+        h.msg_iov = &iov;
+        h.msg_iovlen = 1;
+        h.msg_control = ctl;
+        h.msg_controllen = sizeof ctl;
+        const ssize_t r = recvmsg(fd, &h, MSG_DONTWAIT);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            failed = errno != EAGAIN && errno != EWOULDBLOCK;
+            break;
+        }
+        uint32_t seg = 0;
+        for (cmsghdr *cm = CMSG_FIRSTHDR(&h); cm; cm = CMSG_NXTHDR(&h, cm))
+            if (cm->cmsg_level == SOL_UDP && cm->cmsg_type == UDP_GRO && cm->cmsg_len >= CMSG_LEN(sizeof(uint16_t))) {
+                if (cm->cmsg_len >= CMSG_LEN(sizeof(int))) {
+                    int v;
+                    memcpy(&v, CMSG_DATA(cm), sizeof v);
+                    seg = v > 0 ? (uint32_t)v : 0;
+                } else {
+                    uint16_t v;
+                    memcpy(&v, CMSG_DATA(cm), sizeof v);
+                    seg = v;
+                }
+            }
+        uint32_t len = (uint32_t)r;
+        uint64_t count = qgcm::gro_count(len, seg);
+        if (count > max_n - n) {  // never silent: the datagrams that found no slot are counted
+            cut += count - (max_n - n);
+            count = max_n - n;
+            len = (uint32_t)count * seg;
+        }
+        bufs[nb++] = qgcm_gro_buf{(uint32_t)fill, len, seg, n};
+        n += (uint32_t)count;
+        used = fill + len;
+        fill = (used + 15) & ~(uint64_t)15;
+    }
+    if (out) {
+        out[0] = nb;
+        out[1] = used;
+        out[2] = cut;
+    }
+    return failed && nb == 0 ? -1 : (int)n;
 }
 
 }  // extern "C"

@@ -16,6 +16,8 @@ main.go:41-51              the node's plugins in order  -> Router(plugins=...), 
 plugin/compression.go:31-33, plugin/encryption.go:17-19  the per-peer gate -> peer_plugins_set, plugin_flags
 socket/udp.go:43-47        Write, grouped per peer into UDP_SEGMENT trains -> send_plan, send_plan_host,
                            send_plan_cpu, udp_send_plan
+socket/udp.go:35-41        Read, as coalesced UDP_GRO buffers unpacked into slots -> udp_gro, udp_recv_gro,
+                           gro_unpack, gro_unpack_cpu, route_open_gro_host, route_chain_open_gro_host
 """
 from __future__ import annotations
 
@@ -335,3 +337,56 @@ def udp_send_slots_to(fd: int, arena_ptr: int, stride: int, n: int, lens, peer, 
     """qgcm_udp_send_slots_to: datagram i to addrs[peer[i]]; returns the number sent or -1."""
     return _lib.lib().qgcm_udp_send_slots_to(fd, arena_ptr, stride, n, lens.ctypes.data, peer.ctypes.data,
                                              C.addressof(addrs), n_addrs)
+
+
+def udp_gro(fd: int, on: bool = True) -> None:
+    """qgcm_udp_gro: the UDP_GRO socket option; raises OSError with the kernel's errno."""
+    rc = _lib.lib().qgcm_udp_gro(fd, 1 if on else 0)
+    if rc != 0:
+        import os
+
+        raise OSError(-rc, os.strerror(-rc))
+
+
+def udp_recv_gro(fd: int, packed, bufs, max_n: int, timeout_ms: int, out=None) -> int:
+    """qgcm_udp_recv_gro into `packed` (a contiguous numpy uint8 array, the packed area) and `bufs` (a numpy
+    uint32 array of shape (max_bufs, 4): off, len, seg_len, first per received buffer); `out` a numpy uint64
+    array of 3 ({buffers, bytes used, datagrams cut}) or None.  Returns the number of datagrams, 0 on timeout,
+    or -1."""
+    return _lib.lib().qgcm_udp_recv_gro(fd, packed.ctypes.data, packed.size, bufs.ctypes.data, len(bufs), max_n,
+                                        timeout_ms, None if out is None else out.ctypes.data)
+
+
+def gro_unpack(ctx, packed, packed_len: int, bufs, n_bufs: int, n: int, arena, stride: int, lens, stream=None) -> None:
+    """qgcm_gro_unpack on device tensors: `packed` uint8 (16-B aligned, its size rounded up to 16 B), `bufs`
+    int32 (4 n_bufs), `lens` int32 (n); resolve_incoming follows on the same stream."""
+    _lib.check(_lib.lib().qgcm_gro_unpack(ctx.handle, _ptr(packed), packed_len, _ptr(bufs), n_bufs, n, _ptr(arena),
+                                          stride, _ptr(lens), _stream_handle(stream)), "qgcm_gro_unpack")
+
+
+def gro_unpack_cpu(packed, packed_len: int, bufs, n: int, arena, stride: int, lens) -> None:
+    """qgcm_gro_unpack_cpu over numpy arrays: `packed` / `arena` uint8, `bufs` uint32 (n_bufs, 4), `lens` uint32
+    (n).  Raises for a table whose `first` values are not the prefix sums of its counts."""
+    _lib.check(_lib.lib().qgcm_gro_unpack_cpu(packed.ctypes.data, packed_len, bufs.ctypes.data, len(bufs), n,
+                                              arena.ctypes.data, stride, lens.ctypes.data), "qgcm_gro_unpack_cpu")
+
+
+def route_open_gro_host(ctx, packed, packed_len: int, bufs, arena_ptr: int, stride: int, n: int, lens, peer,
+                        status=None) -> int:
+    """qgcm_route_open_gro_host: route_open_host for what udp_recv_gro left in `packed` and `bufs`; `lens` is
+    output only (the plaintext packet lengths)."""
+    return _lib.check(_lib.lib().qgcm_route_open_gro_host(ctx.handle, packed.ctypes.data, packed_len, bufs.ctypes.data,
+                                                          len(bufs), arena_ptr, stride, n, lens.ctypes.data,
+                                                          peer.ctypes.data,
+                                                          None if status is None else status.ctypes.data),
+                      "qgcm_route_open_gro_host")
+
+
+def route_chain_open_gro_host(ctx, packed, packed_len: int, bufs, arena_ptr: int, stride: int, n: int, lens,
+                              plugins: int, peer, status=None) -> int:
+    """qgcm_route_chain_open_gro_host: route_chain_open_host for what udp_recv_gro left in `packed` and `bufs`."""
+    return _lib.check(_lib.lib().qgcm_route_chain_open_gro_host(ctx.handle, packed.ctypes.data, packed_len,
+                                                                bufs.ctypes.data, len(bufs), arena_ptr, stride, n,
+                                                                lens.ctypes.data, plugins, peer.ctypes.data,
+                                                                None if status is None else status.ctypes.data),
+                      "qgcm_route_chain_open_gro_host")
