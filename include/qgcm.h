@@ -25,6 +25,9 @@
  *   socket/udp.go:35-41 Read() for a batch                    -> qgcm_udp_recv_slots, or coalesced (UDP_GRO):
  *                                                                qgcm_udp_recv_gro + qgcm_gro_unpack /
  *                                                                qgcm_route_chain_open_gro_host
+ *   device/tun.go:60-63 Write(payload) for a batch            -> qgcm_tun_write_slots, or packed on the GPU:
+ *                                                                qgcm_deliver_pack + qgcm_tun_write_packed /
+ *                                                                qgcm_route_chain_open_gro_packed_host
  *
  * Error convention follows the reference's own cgo layer (crypto/dtls.go:37-40, dtls.h:43-48):
  * constructors return NULL and fill a caller-supplied error buffer; everything else returns
@@ -737,6 +740,73 @@ int qgcm_route_open_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t pa
 int qgcm_route_chain_open_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
                                    const qgcm_gro_buf *bufs, uint32_t n_bufs, uint8_t *h_arena, uint64_t stride,
                                    uint32_t n, uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status);
+
+/* ---- delivered packets packed on routed batches: the copy back and the TUN write ---- */
+/* After the incoming chain the delivered packets lie scattered over slots of `stride` bytes, between the
+ * dropped ones and in front of slot tails nobody reads.  The pack lays them back to back -- the mirror of
+ * qgcm_gro_unpack -- so that the copy back and the TUN write move delivered bytes only.
+ *
+ * Packet i of a batch is delivered when d_status[i] == 1 and 4 + d_lens[i] <= stride (d_status == NULL: every
+ * packet has status 1).  A status-1 packet with an impossible length is left out, not clamped, so a bad length
+ * array cannot move the kernel past a slot.  The delivered packets are taken in arena order (index ascending:
+ * no flow is reordered) and numbered k = 0 .. m-1.  Record k is Raw[0 : 4 + L] of its slot -- the 4-byte header
+ * that payload.IPAddress aliases, then the packet, L = d_lens[i] -- padded with zero bytes to
+ * R = (4 + L + 15) & ~15 and placed at off_k, the sum of R over the records before it: every off is a multiple
+ * of 16, as in the receive side's table.  recs[k] = {off_k, L, i, d_peer[i]}; counts = {m, bytes}, bytes the sum
+ * of all R: the full need, even when it does not fit.  A record with off_k + R > packed_cap is not copied and
+ * its entry gets off = 0xffffffff; these records form a suffix, because offsets ascend.  Every byte of
+ * [0, min(bytes, the end of the last record that fits)) of the packed area is determined, zero padding
+ * included; every byte behind it is untouched; recs entries past m are unspecified.  A delivered empty packet
+ * (L == 0) is a 16-byte record.
+ *
+ * qgcm_deliver_pack: device arrays, asynchronous on stream, no context state (calls on several streams may run
+ * at once).  stride a nonzero multiple of 4 and d_arena 4-B aligned (a stride that is a multiple of 16 under a
+ * 16-B-aligned arena takes the 16-byte path, anything else the dword path); d_lens and d_peer 4-B aligned,
+ * d_status any alignment or NULL; d_packed and d_recs (n entries) 16-B aligned, d_counts (two uint64) 8-B
+ * aligned; d_work qgcm_deliver_pack_work(n) bytes of device memory, 16-B aligned, the call's own until it has
+ * run.  Nothing at or past slot * stride + stride is read, nothing at or past packed_cap is written.  n == 0:
+ * counts = {0, 0}, nothing else launched.  n > QGCM_MAX_BATCH, a bad stride, packed_cap above 2^32 - 16 (off is
+ * 32 bits), a NULL or misaligned pointer: QGCM_E_ARG, nothing launched.
+ * qgcm_deliver_pack_cpu: the same contract for host arrays (no alignment asked), by the host, so that a worker
+ * on qgcm_route_chain_open_host can pack for qgcm_tun_write_packed.
+ *
+ * qgcm_tun_write_packed: qgcm_tun_write_slots for a packed batch: writes packed[off + 4 .. off + 4 + len) of
+ * records 0 .. m-1 in order; a packet the kernel rejects ends the batch there and EINTR is retried, as in
+ * qgcm_tun_write_slots.  The whole table is checked first: every off + 4 + len <= packed_len, otherwise -1 with
+ * nothing written (a record that did not fit, off = 0xffffffff, fails that check).  Returns the number written
+ * (m on success) or -1 when none was.
+ *
+ * qgcm_route_chain_open_packed_host / qgcm_route_chain_open_gro_packed_host: qgcm_route_chain_open_host /
+ * qgcm_route_chain_open_gro_host with the copy back replaced.  Chunks, serialisation and the order of resolve,
+ * chain and accounting are theirs.  Per chunk the delivered packets are packed into an area the context owns
+ * (cn * round16(stride) bytes, grown on demand: the device pack always fits) and the chunk's counts come down.
+ * If its bytes do not fit behind the fill position of h_out, the call returns QGCM_E_NOMEM before that chunk is
+ * accounted or copied: the caller's input is whole and the call can be repeated from packet out[0] on (the GRO
+ * form: from that packet's buffer, which is a chunk's first, with a table rebased so that it is again a prefix
+ * sum from 0).  Otherwise the chunk is accounted and its bytes and records are appended to h_out (16-B steps)
+ * and h_recs (n entries), `off` rebased by the fill position and `slot` by the chunk's first slot: the table is
+ * the one qgcm_deliver_pack_cpu makes of the whole batch.  h_peer, h_status and h_lens come back for all n
+ * packets as from the existing calls; the slots-in form reads h_arena and never writes it.  out = {packets
+ * fully processed, records written, bytes of h_out used}, written on success and on QGCM_E_NOMEM.  out_cap
+ * above 2^32 - 16 counts as 2^32 - 16.  Returns the number of drops or a negative error.  Only the chain forms
+ * have a packed variant: the plain open's lengths are datagram lengths, and a chain with
+ * QGCM_PLUGIN_ENCRYPTION alone is that call. */
+typedef struct qgcm_pack_rec { uint32_t off, len, slot, peer; } qgcm_pack_rec;
+uint64_t qgcm_deliver_pack_work(uint32_t n);
+int qgcm_deliver_pack(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+                      const uint32_t *d_peer, const uint8_t *d_status, uint8_t *d_packed, uint64_t packed_cap,
+                      qgcm_pack_rec *d_recs, uint64_t *d_counts, void *d_work, void *stream);
+int qgcm_deliver_pack_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens, const uint32_t *peer,
+                          const uint8_t *status, uint8_t *packed, uint64_t packed_cap, qgcm_pack_rec *recs,
+                          uint64_t counts[2]);
+int qgcm_tun_write_packed(int fd, const uint8_t *packed, uint64_t packed_len, const qgcm_pack_rec *recs, uint32_t m);
+int qgcm_route_chain_open_packed_host(qgcm_ctx *ctx, const uint8_t *h_arena, uint64_t stride, uint32_t n,
+                                      uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
+                                      uint8_t *h_out, uint64_t out_cap, qgcm_pack_rec *h_recs, uint64_t out[3]);
+int qgcm_route_chain_open_gro_packed_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
+                                          const qgcm_gro_buf *bufs, uint32_t n_bufs, uint64_t stride, uint32_t n,
+                                          uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
+                                          uint8_t *h_out, uint64_t out_cap, qgcm_pack_rec *h_recs, uint64_t out[3]);
 
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19

@@ -44,6 +44,8 @@ EXPORTS = (
     "qgcm_send_plan_work", "qgcm_send_plan", "qgcm_send_plan_cpu", "qgcm_send_plan_host", "qgcm_udp_send_plan",
     "qgcm_udp_gro", "qgcm_udp_recv_gro", "qgcm_gro_unpack", "qgcm_gro_unpack_cpu",
     "qgcm_route_open_gro_host", "qgcm_route_chain_open_gro_host",
+    "qgcm_deliver_pack_work", "qgcm_deliver_pack", "qgcm_deliver_pack_cpu", "qgcm_tun_write_packed",
+    "qgcm_route_chain_open_packed_host", "qgcm_route_chain_open_gro_packed_host",
 )
 
 QGCM_OK = 0
@@ -116,6 +118,12 @@ class GroBuf(C.Structure):
     16 bytes."""
 
     _fields_ = [("off", C.c_uint32), ("len", C.c_uint32), ("seg_len", C.c_uint32), ("first", C.c_uint32)]
+
+
+class PackRec(C.Structure):
+    """qgcm_pack_rec: {off (0xffffffff: the record did not fit), len, slot, peer} -- 16 bytes."""
+
+    _fields_ = [("off", C.c_uint32), ("len", C.c_uint32), ("slot", C.c_uint32), ("peer", C.c_uint32)]
 
 
 _lib: C.CDLL | None = None
@@ -252,6 +260,14 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_gro_unpack_cpu.argtypes = [vp, u64, vp, u32, u32, vp, u64, vp]
         L.qgcm_route_open_gro_host.argtypes = [vp, vp, u64, vp, u32, vp, u64, u32, vp, vp, vp]
         L.qgcm_route_chain_open_gro_host.argtypes = [vp, vp, u64, vp, u32, vp, u64, u32, vp, u32, vp, vp]
+    if hasattr(L, "qgcm_deliver_pack"):  # (older builds loaded by the A/B tools lack the delivered-packet pack)
+        L.qgcm_deliver_pack_work.argtypes = [u32]
+        L.qgcm_deliver_pack_work.restype = u64
+        L.qgcm_deliver_pack.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, vp]
+        L.qgcm_deliver_pack_cpu.argtypes = [vp, u64, u32, vp, vp, vp, vp, u64, vp, vp]
+        L.qgcm_tun_write_packed.argtypes = [C.c_int, vp, u64, vp, u32]
+        L.qgcm_route_chain_open_packed_host.argtypes = [vp, vp, u64, u32, vp, u32, vp, vp, vp, u64, vp, vp]
+        L.qgcm_route_chain_open_gro_packed_host.argtypes = [vp, vp, u64, vp, u32, u64, u32, vp, u32, vp, vp, vp, u64, vp, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

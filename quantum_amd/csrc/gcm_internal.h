@@ -389,6 +389,14 @@ hipError_t launch_send_plan(uint32_t n, uint32_t max_keys, const uint32_t *lens,
 // has checked the arguments.  n == 0 or n_bufs == 0 launches nothing.
 hipError_t launch_gro_unpack(const uint8_t *packed, uint64_t packed_len, const qgcm_gro_buf *bufs, uint32_t n_bufs,
                              uint32_t n, uint8_t *arena, uint64_t stride, uint32_t *lens, hipStream_t s);
+// Delivered packets packed back to back (pack_kernels.hip; include/qgcm.h "delivered packets packed on routed
+// batches"): tile summaries, spine, emit and the copy on s (the 16-byte path when stride and arena allow it,
+// else the dword path); work: deliver_pack_work_bytes(n) bytes, 16-B aligned; the caller has checked the
+// arguments.  n == 0 writes counts = {0, 0} and launches nothing.
+uint64_t deliver_pack_work_bytes(uint32_t n);
+hipError_t launch_deliver_pack(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens, const uint32_t *peer,
+                               const uint8_t *status, uint8_t *packed, uint64_t packed_cap, qgcm_pack_rec *recs,
+                               uint64_t *counts, void *work, hipStream_t s);
 // qgcm_send_plan_host plans on the device from this many packets on (QGCM_PLAN_DEVICE_MIN at qgcm_create): the
 // measured crossover -- 181 against 186 us at 65536, 319 against 993 us at 262144
 constexpr uint32_t kPlanDeviceMin = 65536;

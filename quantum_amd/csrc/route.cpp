@@ -19,6 +19,7 @@
 #include "../../include/qgcm.h"
 #include "gcm_internal.h"
 #include "gro_core.h"
+#include "pack_core.h"
 #include "send_plan_core.h"
 
 namespace qgcm {
@@ -55,6 +56,11 @@ struct RouteState {
     uint8_t *d_gro = nullptr;
     size_t gro_cap = 0;
     std::vector<qgcm_gro_buf> h_gro;
+
+    // the packed pipelines: a chunk's records, counts, scan work area and packed bytes on the device (under
+    // pipe_mu, on `stream`)
+    uint8_t *d_pack = nullptr;
+    size_t pack_cap = 0;
 };
 
 RouteState *route_state_create() {
@@ -73,6 +79,7 @@ void route_state_destroy(RouteState *r) {
     hipFree(r->d_side);
     hipFree(r->d_plan);
     hipFree(r->d_gro);
+    hipFree(r->d_pack);
     if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
@@ -219,12 +226,83 @@ int account(qgcm_ctx *ctx, int dir, uint32_t n, const uint32_t *d_peer, const qg
     return hip_rc(launch_route_account(a, ctx_num_cus(ctx), s));
 }
 
+// The copy back of the packed pipelines (include/qgcm.h "delivered packets packed on routed batches"): where
+// the caller's packed area and table are, and how far they are filled.
+struct PackOut {
+    uint8_t *h_out;
+    uint64_t out_cap;  // at most kPackMaxCap: `off` is 32 bits
+    qgcm_pack_rec *h_recs;
+    uint64_t *out;     // {packets fully processed, records written, bytes of h_out used}
+    uint64_t fill = 0, m = 0;
+    // the device area of a chunk
+    qgcm_pack_rec *d_recs = nullptr;
+    uint64_t *d_counts = nullptr;
+    void *d_work = nullptr;
+    uint8_t *d_packed = nullptr;
+    uint64_t h_counts[2] = {0, 0};
+};
+
+inline uint64_t pack_area_bytes(uint32_t cn, uint64_t stride) {
+    return std::min<uint64_t>((uint64_t)cn * ((stride + 15) & ~(uint64_t)15), kPackMaxCap);
+}
+
+// recs (16-B aligned first), counts, the scan's work area, the packed bytes (16-B aligned)
+bool pack_grow(RouteState *r, PackOut &pk, uint32_t max_cn, uint64_t stride) {
+    const size_t o_counts = 16ull * max_cn, o_work = o_counts + 16, o_packed = o_work + (size_t)deliver_pack_work_bytes(max_cn);
+    if (!grow(r->d_pack, r->pack_cap, o_packed + std::max<size_t>((size_t)pack_area_bytes(max_cn, stride), 16))) return false;
+    pk.d_recs = reinterpret_cast<qgcm_pack_rec *>(r->d_pack);
+    pk.d_counts = reinterpret_cast<uint64_t *>(r->d_pack + o_counts);
+    pk.d_work = r->d_pack + o_work;
+    pk.d_packed = r->d_pack + o_packed;
+    return true;
+}
+
+// A chunk's delivered packets packed on the device, behind its chain on s; its counts come down.  QGCM_E_NOMEM
+// (out written) when the chunk's bytes do not fit behind the fill position: nothing of it is accounted or copied.
+int pack_chunk(PackOut &pk, const uint8_t *d_arena, uint64_t stride, uint32_t c0, uint32_t cn, const uint32_t *d_lens,
+               const uint32_t *d_peer, const uint8_t *d_stat, hipStream_t s) {
+    if (launch_deliver_pack(d_arena, stride, cn, d_lens, d_peer, d_stat, pk.d_packed, pack_area_bytes(cn, stride), pk.d_recs,
+                            pk.d_counts, pk.d_work, s) != hipSuccess ||
+        hipMemcpyAsync(pk.h_counts, pk.d_counts, 16, hipMemcpyDeviceToHost, s) != hipSuccess)
+        return QGCM_E_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess || pk.h_counts[0] > cn) return QGCM_E_HIP;
+    pk.out[0] = c0;
+    pk.out[1] = pk.m;
+    pk.out[2] = pk.fill;
+    // a chunk whose records did not all fit the device area (slots of more than 4 GiB) cannot be delivered
+    if (pk.h_counts[1] > pack_area_bytes(cn, stride) || pk.fill + pk.h_counts[1] > pk.out_cap) return QGCM_E_NOMEM;
+    return QGCM_OK;
+}
+
+// ... and, once the chunk is accounted, its bytes and records appended to the caller's
+bool pack_copy_back(PackOut &pk, hipStream_t s) {
+    const uint64_t m = pk.h_counts[0], bytes = pk.h_counts[1];
+    return (!bytes || hipMemcpyAsync(pk.h_out + pk.fill, pk.d_packed, (size_t)bytes, hipMemcpyDeviceToHost, s) == hipSuccess) &&
+           (!m || hipMemcpyAsync(pk.h_recs + pk.m, pk.d_recs, 16ull * m, hipMemcpyDeviceToHost, s) == hipSuccess);
+}
+
+// ... and, once they have arrived, rebased: `off` by the fill position, `slot` by the chunk's first slot
+void pack_rebase(PackOut &pk, uint32_t c0, uint32_t cn) {
+    const uint64_t m = pk.h_counts[0];
+    if (pk.fill || c0)
+        for (uint64_t k = pk.m; k < pk.m + m; ++k) {
+            pk.h_recs[k].off += (uint32_t)pk.fill;
+            pk.h_recs[k].slot += c0;
+        }
+    pk.m += m;
+    pk.fill += pk.h_counts[1];
+    pk.out[0] = (uint64_t)c0 + cn;
+    pk.out[1] = pk.m;
+    pk.out[2] = pk.fill;
+}
+
 // Outgoing.pipeline / Incoming.pipeline for a batch in host memory: chunks of at most kRouteChunk packets,
 // copy in -> resolve -> seal or open (chain: the plugin chain under the node's `plugins`) -> account -> copy
-// back, on one stream.
+// back, on one stream.  With `pk` (the incoming chain only) the copy back is the packed one: the pack runs
+// behind the chain, its counts are waited for before the chunk is accounted, and the arena stays on the device.
 int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
                    const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status, bool chain = false,
-                   uint32_t plugins = 0) {
+                   uint32_t plugins = 0, PackOut *pk = nullptr) {
     if (!ctx) return QGCM_E_ARG;
     RouteState *r = ctx_route(ctx);
     if ((stride & 3) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
@@ -253,6 +331,7 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
                  o_bytes = (o_stat + chunk + 15) & ~(size_t)15, o_work = o_bytes + 4 * (size_t)chain_work_lanes(chunk),
                  side = chain ? o_work + QGCM_CHAIN_WORK(chunk) : o_stat + chunk;
     if (!grow(r->d_arena, r->arena_cap, (size_t)chunk * stride) || !grow(r->d_side, r->side_cap, side)) return QGCM_E_NOMEM;
+    if (pk && !pack_grow(r, *pk, chunk, stride)) return QGCM_E_NOMEM;
     r->h_stat.resize(chunk);
     qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
     uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
@@ -272,6 +351,7 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
         if (rc == QGCM_OK && chain) {
             rc = run_chain(ctx, seal, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, nonces, d_stat, d_bytes,
                            r->d_side + o_work, s);
+            if (rc == QGCM_OK && pk) rc = pack_chunk(*pk, r->d_arena, stride, c0, cn, d_lens, d_peer, d_stat, s);
             if (rc == QGCM_OK) rc = account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
         } else if (rc == QGCM_OK) {
             rc = seal ? qgcm_seal_batch(ctx, r->d_arena, d_descs, cn, nonces, 4, d_stat, s)
@@ -279,7 +359,8 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
             if (rc == QGCM_OK) rc = qgcm_route_account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, d_descs, d_stat, s);
         }
         if (rc == QGCM_OK &&
-            (hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            ((pk ? !pack_copy_back(*pk, s)
+                 : hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess) ||
              hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
              hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
              // the chain's lengths are final on the device (the tables of include/qgcm.h)
@@ -287,6 +368,7 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
             rc = QGCM_E_HIP;
         if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
         if (rc != QGCM_OK) return rc;
+        if (pk) pack_rebase(*pk, c0, cn);
         for (uint32_t i = 0; i < cn; ++i) {
             const bool ok = r->h_stat[i] == 1;
             if (chain) {
@@ -312,11 +394,11 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
 // past packed_len) are datagrams of length 0.
 int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gro_buf *bufs,
                        uint32_t n_bufs, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens, uint32_t *h_peer,
-                       uint8_t *h_status, bool chain, uint32_t plugins) {
+                       uint8_t *h_status, bool chain, uint32_t plugins, PackOut *pk = nullptr) {
     if (!ctx) return QGCM_E_ARG;
     RouteState *r = ctx_route(ctx);
     if ((stride & 3) || n > QGCM_MAX_BATCH || n_bufs > n) return QGCM_E_ARG;
-    if (n && (!h_packed || !bufs || !h_arena || !h_lens || !h_peer || stride == 0)) return QGCM_E_ARG;
+    if (n && (!h_packed || !bufs || (!h_arena && !pk) || !h_lens || !h_peer || stride == 0)) return QGCM_E_ARG;
     if (chain && (plugins & ~kAllPlugins)) return QGCM_E_ARG;
     if (!gro_table_ok(bufs, n_bufs, n)) return QGCM_E_ARG;
     {
@@ -364,7 +446,7 @@ int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_l
                  side = chain ? o_work + QGCM_CHAIN_WORK(max_cn) : o_stat + max_cn;
     const size_t o_packed = 16ull * max_nb, gro = o_packed + (size_t)((max_span + 15) & ~(uint64_t)15);
     if (!grow(r->d_arena, r->arena_cap, (size_t)max_cn * stride) || !grow(r->d_side, r->side_cap, side) ||
-        !grow(r->d_gro, r->gro_cap, std::max<size_t>(gro, 16)))
+        !grow(r->d_gro, r->gro_cap, std::max<size_t>(gro, 16)) || (pk && !pack_grow(r, *pk, max_cn, stride)))
         return QGCM_E_NOMEM;
     r->h_stat.resize(max_cn);
     r->h_gro.resize(max_nb);
@@ -385,7 +467,7 @@ int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_l
             r->h_gro[j] = past ? qgcm_gro_buf{0xffffffffu, 1, 0, b.first - c0}
                                : qgcm_gro_buf{(uint32_t)(b.off - c.lo), b.len, b.seg_len, b.first - c0};
         }
-        uint8_t *h = h_arena + (uint64_t)c0 * stride;
+        uint8_t *h = pk ? nullptr : h_arena + (uint64_t)c0 * stride;
         if (hipMemsetAsync(d_lens, 0, 4ull * cn, s) != hipSuccess ||
             (c.hi > c.lo && hipMemcpyAsync(d_packed, h_packed + c.lo, (size_t)(c.hi - c.lo), hipMemcpyHostToDevice, s) != hipSuccess) ||
             hipMemcpyAsync(d_bufs, r->h_gro.data(), 16ull * nb, hipMemcpyHostToDevice, s) != hipSuccess)
@@ -395,6 +477,7 @@ int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_l
         if (rc == QGCM_OK && chain) {
             rc = run_chain(ctx, false, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, nullptr, d_stat, d_bytes,
                            r->d_side + o_work, s);
+            if (rc == QGCM_OK && pk) rc = pack_chunk(*pk, r->d_arena, stride, c0, cn, d_lens, d_peer, d_stat, s);
             if (rc == QGCM_OK) rc = account(ctx, QGCM_RX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
         } else if (rc == QGCM_OK) {
             rc = qgcm_open_batch(ctx, r->d_arena, d_descs, cn, 4, d_stat, s);
@@ -402,13 +485,15 @@ int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_l
         }
         // the lengths come back in both forms: the chain's are final, the open's are the datagrams'
         if (rc == QGCM_OK &&
-            (hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            ((pk ? !pack_copy_back(*pk, s)
+                 : hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess) ||
              hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
              hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
              hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess))
             rc = QGCM_E_HIP;
         if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
         if (rc != QGCM_OK) return rc;
+        if (pk) pack_rebase(*pk, c0, cn);
         for (uint32_t i = 0; i < cn; ++i) {
             const bool ok = r->h_stat[i] == 1;
             if (!chain) h_lens[c0 + i] = ok ? h_lens[c0 + i] - 4 - QGCM_OVERHEAD : 0;
@@ -639,6 +724,43 @@ int qgcm_route_chain_open_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint6
                                    uint32_t n, uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status) {
     return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, h_arena, stride, n, h_lens, h_peer, h_status, true,
                               plugins);
+}
+
+uint64_t qgcm_deliver_pack_work(uint32_t n) { return deliver_pack_work_bytes(n); }
+
+int qgcm_deliver_pack(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+                      const uint32_t *d_peer, const uint8_t *d_status, uint8_t *d_packed, uint64_t packed_cap,
+                      qgcm_pack_rec *d_recs, uint64_t *d_counts, void *d_work, void *stream) {
+    if (!ctx || n > QGCM_MAX_BATCH || (stride & 3) || packed_cap > kPackMaxCap || !d_counts) return QGCM_E_ARG;
+    if (n && (!d_arena || !d_lens || !d_peer || !d_packed || !d_recs || !d_work || stride == 0)) return QGCM_E_ARG;
+    if (((uintptr_t)d_arena & 3) || ((uintptr_t)d_lens & 3) || ((uintptr_t)d_peer & 3) || ((uintptr_t)d_packed & 15) ||
+        ((uintptr_t)d_recs & 15) || ((uintptr_t)d_counts & 7) || ((uintptr_t)d_work & 15))
+        return QGCM_E_ARG;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    return hip_rc(launch_deliver_pack(d_arena, stride, n, d_lens, d_peer, d_status, d_packed, packed_cap, d_recs, d_counts,
+                                      d_work, (hipStream_t)stream));
+}
+
+int qgcm_route_chain_open_packed_host(qgcm_ctx *ctx, const uint8_t *h_arena, uint64_t stride, uint32_t n,
+                                      uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
+                                      uint8_t *h_out, uint64_t out_cap, qgcm_pack_rec *h_recs, uint64_t out[3]) {
+    if (!out || (n && (!h_out || !h_recs))) return QGCM_E_ARG;
+    out[0] = out[1] = out[2] = 0;
+    PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), h_recs, out};
+    // the arena is only read: with `pk` the copy back never names it
+    return run_route_host(ctx, false, const_cast<uint8_t *>(h_arena), stride, n, h_lens, nullptr, h_peer, h_status, true,
+                          plugins, &pk);
+}
+
+int qgcm_route_chain_open_gro_packed_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
+                                          const qgcm_gro_buf *bufs, uint32_t n_bufs, uint64_t stride, uint32_t n,
+                                          uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
+                                          uint8_t *h_out, uint64_t out_cap, qgcm_pack_rec *h_recs, uint64_t out[3]) {
+    if (!out || (n && (!h_out || !h_recs))) return QGCM_E_ARG;
+    out[0] = out[1] = out[2] = 0;
+    PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), h_recs, out};
+    return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, nullptr, stride, n, h_lens, h_peer, h_status, true,
+                              plugins, &pk);
 }
 
 int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]) {

@@ -34,6 +34,7 @@
 #include <atomic>
 
 #include "../../include/qgcm.h"
+#include "pack_core.h"
 
 namespace {
 
@@ -349,6 +350,24 @@ int qgcm_tun_write_slots(int fd, const uint8_t *arena, uint64_t stride, uint32_t
         ++done;
     }
     return done || n == 0 ? (int)done : -1;
+}
+
+// qgcm_tun_write_slots for a packed batch (include/qgcm.h "delivered packets packed on routed batches"):
+// packed[off + 4 .. off + 4 + len) of records 0..m-1 in order, the same rule for a rejected packet and for
+// EINTR.  The whole table is checked before the first write: a record that reaches past packed_len (one that
+// did not fit, off = 0xffffffff, among them) returns -1 with nothing written.
+int qgcm_tun_write_packed(int fd, const uint8_t *packed, uint64_t packed_len, const qgcm_pack_rec *recs, uint32_t m) {
+    if (fd < 0 || (m && (!packed || !recs)) || !qgcm::pack_table_ok(recs, m, packed_len)) return -1;
+    uint32_t done = 0;
+    while (done < m) {
+        const ssize_t w = write(fd, packed + recs[done].off + kPacketStart, recs[done].len);
+        if (w < 0) {
+            if (errno == EINTR) continue;
+            break;
+        }
+        ++done;
+    }
+    return done || m == 0 ? (int)done : -1;
 }
 
 int qgcm_tun_close(int fd) { return close(fd) == 0 ? 0 : -1; }

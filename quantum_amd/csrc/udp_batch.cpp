@@ -22,6 +22,7 @@
 
 #include "../../include/qgcm.h"
 #include "gro_core.h"
+#include "pack_core.h"
 
 #ifndef UDP_SEGMENT
 #define UDP_SEGMENT 103  // linux/udp.h, Linux 4.18
@@ -433,6 +434,18 @@ int qgcm_udp_recv_gro(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_gro_buf
         out[2] = cut;
     }
     return failed && nb == 0 ? -1 : (int)n;
+}
+
+// The delivered packets of an opened batch packed back to back by the host (pack_core.h; the contract of
+// qgcm_deliver_pack, no alignment asked): what a worker on qgcm_route_chain_open_host hands to
+// qgcm_tun_write_packed.
+int qgcm_deliver_pack_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens, const uint32_t *peer,
+                          const uint8_t *status, uint8_t *packed, uint64_t packed_cap, qgcm_pack_rec *recs,
+                          uint64_t counts[2]) {
+    if (n > QGCM_MAX_BATCH || (stride & 3) || packed_cap > qgcm::kPackMaxCap || !counts) return QGCM_E_ARG;
+    if (n && (!arena || !lens || !peer || !packed || !recs || stride == 0)) return QGCM_E_ARG;
+    qgcm::deliver_pack_cpu(arena, stride, n, lens, peer, status, packed, packed_cap, recs, counts);
+    return QGCM_OK;
 }
 
 }  // extern "C"

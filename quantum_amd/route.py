@@ -18,6 +18,9 @@ socket/udp.go:43-47        Write, grouped per peer into UDP_SEGMENT trains -> se
                            send_plan_cpu, udp_send_plan
 socket/udp.go:35-41        Read, as coalesced UDP_GRO buffers unpacked into slots -> udp_gro, udp_recv_gro,
                            gro_unpack, gro_unpack_cpu, route_open_gro_host, route_chain_open_gro_host
+device/tun.go:60-63        Write, from delivered packets packed back to back on the GPU -> deliver_pack,
+                           deliver_pack_cpu, tun_write_packed, route_chain_open_packed_host,
+                           route_chain_open_gro_packed_host
 """
 from __future__ import annotations
 
@@ -390,3 +393,87 @@ def route_chain_open_gro_host(ctx, packed, packed_len: int, bufs, arena_ptr: int
                                                                 lens.ctypes.data, plugins, peer.ctypes.data,
                                                                 None if status is None else status.ctypes.data),
                       "qgcm_route_chain_open_gro_host")
+
+
+PACK_NO_ROOM = 0xFFFFFFFF  # `off` of a record that did not fit below packed_cap
+
+
+def deliver_pack_work(n: int, device="cuda"):
+    """A work area for a deliver_pack call of n packets (qgcm_deliver_pack_work(n) bytes; torch allocations are
+    16-B aligned)."""
+    import torch
+
+    return torch.empty(int(_lib.lib().qgcm_deliver_pack_work(n)), dtype=torch.uint8, device=device)
+
+
+def deliver_pack(ctx, arena, stride: int, n: int, lens, peer, status, packed, packed_cap: int, recs, counts, work,
+                 stream=None) -> None:
+    """qgcm_deliver_pack after chain_incoming on the same stream: `lens` / `peer` int32 (n), `status` uint8 (n) or
+    None, `packed` uint8 (16-B aligned), `recs` int32 (4 n: off, len, slot, peer per record), `counts` int64 (2:
+    m, bytes), `work` from deliver_pack_work(n)."""
+    _lib.check(_lib.lib().qgcm_deliver_pack(ctx.handle, _ptr(arena), stride, n, _ptr(lens), _ptr(peer), _ptr(status),
+                                            _ptr(packed), packed_cap, _ptr(recs), _ptr(counts), _ptr(work),
+                                            _stream_handle(stream)), "qgcm_deliver_pack")
+
+
+def deliver_pack_cpu(arena, stride: int, n: int, lens, peer, status, packed, recs=None):
+    """qgcm_deliver_pack_cpu over numpy arrays: `arena` / `packed` uint8 (packed_cap = packed.size), `lens` /
+    `peer` uint32 (n), `status` uint8 (n) or None -> (recs[:m] a (m, 4) uint32 array of off, len, slot, peer;
+    bytes, the full need).  `packed` is written in place."""
+    import numpy as np
+
+    if recs is None:
+        recs = np.zeros((max(1, n), 4), np.uint32)
+    counts = np.zeros(2, np.uint64)
+    _lib.check(_lib.lib().qgcm_deliver_pack_cpu(arena.ctypes.data, stride, n, lens.ctypes.data, peer.ctypes.data,
+                                                None if status is None else status.ctypes.data, packed.ctypes.data,
+                                                packed.size, recs.ctypes.data, counts.ctypes.data),
+               "qgcm_deliver_pack_cpu")
+    return recs[:int(counts[0])], int(counts[1])
+
+
+def tun_write_packed(fd: int, packed, packed_len: int, recs) -> int:
+    """qgcm_tun_write_packed: Raw[4 : 4 + len] of every record of `recs` (numpy uint32 (m, 4)) to the queue, in
+    order; returns the number written or -1."""
+    return _lib.lib().qgcm_tun_write_packed(fd, packed.ctypes.data, packed_len, recs.ctypes.data, len(recs))
+
+
+def _packed_result(rc: int, what: str, recs, out):
+    if rc < 0 and rc != _lib.QGCM_E_NOMEM:
+        _lib.check(rc, what)
+    return rc, recs[:int(out[1])], out
+
+
+def route_chain_open_packed_host(ctx, arena_ptr: int, stride: int, n: int, lens, plugins: int, peer, status, out_buf,
+                                 recs=None):
+    """qgcm_route_chain_open_packed_host: route_chain_open_host whose delivered packets come back packed into
+    `out_buf` (a numpy uint8 array, 16-B aligned storage not asked) -> (rc, recs[:m], out): rc the number of drops
+    or QGCM_E_NOMEM (out_buf too small: out[0] packets are done, repeat from there), recs a (m, 4) uint32 array,
+    out = {packets fully processed, records written, bytes of out_buf used}."""
+    import numpy as np
+
+    if recs is None:
+        recs = np.zeros((max(1, n), 4), np.uint32)
+    out = np.zeros(3, np.uint64)
+    rc = _lib.lib().qgcm_route_chain_open_packed_host(ctx.handle, arena_ptr, stride, n, lens.ctypes.data, plugins,
+                                                      peer.ctypes.data, None if status is None else status.ctypes.data,
+                                                      out_buf.ctypes.data, out_buf.size, recs.ctypes.data, out.ctypes.data)
+    return _packed_result(rc, "qgcm_route_chain_open_packed_host", recs, out)
+
+
+def route_chain_open_gro_packed_host(ctx, packed, packed_len: int, bufs, stride: int, n: int, lens, plugins: int, peer,
+                                     status, out_buf, recs=None):
+    """qgcm_route_chain_open_gro_packed_host: route_chain_open_gro_host whose delivered packets come back packed;
+    returns as route_chain_open_packed_host."""
+    import numpy as np
+
+    if recs is None:
+        recs = np.zeros((max(1, n), 4), np.uint32)
+    out = np.zeros(3, np.uint64)
+    rc = _lib.lib().qgcm_route_chain_open_gro_packed_host(ctx.handle, packed.ctypes.data, packed_len, bufs.ctypes.data,
+                                                          len(bufs), stride, n, lens.ctypes.data, plugins,
+                                                          peer.ctypes.data,
+                                                          None if status is None else status.ctypes.data,
+                                                          out_buf.ctypes.data, out_buf.size, recs.ctypes.data,
+                                                          out.ctypes.data)
+    return _packed_result(rc, "qgcm_route_chain_open_gro_packed_host", recs, out)
