@@ -21,7 +21,10 @@
  *                         -> qgcm_peer_plugins_set + qgcm_chain_outgoing / qgcm_chain_incoming,
  *                            qgcm_route_account_bytes, qgcm_route_chain_seal_host / qgcm_route_chain_open_host
  *   socket/udp.go:44-47 Write(payload, mapping)               -> qgcm_udp_send_slots_to, or grouped per peer:
- *                                                                qgcm_send_plan + qgcm_udp_send_plan
+ *                                                                qgcm_send_plan + qgcm_udp_send_plan, or with
+ *                                                                the trains packed on the GPU: qgcm_train_pack +
+ *                                                                qgcm_udp_send_packed /
+ *                                                                qgcm_route_chain_seal_packed_host
  *   socket/udp.go:35-41 Read() for a batch                    -> qgcm_udp_recv_slots, or coalesced (UDP_GRO):
  *                                                                qgcm_udp_recv_gro + qgcm_gro_unpack /
  *                                                                qgcm_route_chain_open_gro_host
@@ -807,6 +810,84 @@ int qgcm_route_chain_open_gro_packed_host(qgcm_ctx *ctx, const uint8_t *h_packed
                                           const qgcm_gro_buf *bufs, uint32_t n_bufs, uint64_t stride, uint32_t n,
                                           uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
                                           uint8_t *h_out, uint64_t out_cap, qgcm_pack_rec *h_recs, uint64_t out[3]);
+
+/* ---- planned trains packed on routed batches: one iovec a train, own-size copy back ---- */
+/* After the outgoing chain the sealed datagrams lie in slots of `stride` bytes and the plan of qgcm_send_plan
+ * names them train by train.  The pack lays every train's datagrams back to back -- the mirror of
+ * qgcm_gro_unpack: aligned slots to unaligned destinations -- so that the copy back moves datagram bytes only
+ * and the sender hands the kernel one iovec a train.  A qgcm_ptrain is a qgcm_train with `first` replaced by
+ * the byte offset `off` of the train in the packed area.
+ *
+ * Inputs: an arena of n slots of `stride` bytes and a plan as qgcm_send_plan leaves it: order[0..m),
+ * trains[0..t), counts = {m, t}.  Train j holds its `count` datagrams with no gaps: datagram k is
+ * Raw[0 : seg_len] of slot order[first + k] and sits at off_j + k * seg_len; the train is padded with zero bytes
+ * to R_j = (count * seg_len + 15) & ~15, and off_j is the sum of R over the trains before it, so every off is a
+ * multiple of 16.  ptrains[j] = {off_j, count, peer, seg_len}; pcounts = {t, bytes}, bytes the sum of all R: the
+ * full need, even when it does not fit.  A train with off_j + R_j > packed_cap is not copied and its entry gets
+ * off = 0xffffffff; these trains form a suffix, because offsets ascend.  Every byte of [0, the end of the last
+ * train that fits) of the packed area is determined, zero padding included; every byte behind it is untouched;
+ * ptrains entries past t are unspecified.  The pack does not read the batch's lengths: the plan's seg_len is the
+ * length, and the plan guarantees the two are equal.
+ *
+ * A plan is well-formed when m <= n and t <= m, the trains tile [0, m) in order (each `first` the sum of the
+ * counts before it, the counts total m), every count is in [1, 1024], every seg_len in [1, stride] and every
+ * order[p] < n.  qgcm_train_pack reads the plan from device memory and cannot refuse it, so it stays memory-safe
+ * on any plan: m and t as read from d_plan_counts are clamped to n; a train with a count or seg_len out of
+ * range, or with first + count > m (in 64 bits), is void: its size is 0 and its off 0xffffffff; a member with
+ * order[p] >= n is packed as seg_len zero bytes, no slot is read for it.  For a plan that does not tile the
+ * packed bytes are unspecified.  In every case nothing outside the arena's n * stride bytes is read (and of a
+ * slot nothing at or past min(round16(seg_len), stride)), and nothing at or past packed_cap is written.
+ *
+ * qgcm_train_pack: device arrays, asynchronous on stream, no context state (calls on several streams may run
+ * at once).  It reads m and t on the device, so it follows qgcm_send_plan on the same stream with no host
+ * synchronisation in between.  stride a nonzero multiple of 4 and d_arena 4-B aligned (a stride that is a
+ * multiple of 16 under a 16-B-aligned arena takes the 16-byte path, anything else the dword path); d_order and
+ * d_plan_counts (two uint32) 4-B aligned; d_trains, d_packed and d_ptrains (n entries) 16-B aligned; d_pcounts
+ * (two uint64) 8-B aligned; d_work qgcm_train_pack_work(n) bytes of device memory, 16-B aligned, the call's own
+ * until it has run.  n == 0: pcounts = {0, 0}, nothing else launched.  n > QGCM_MAX_BATCH, a bad stride,
+ * packed_cap above 2^32 - 16 (off is 32 bits), a NULL or misaligned pointer: QGCM_E_ARG, nothing launched.
+ * qgcm_train_pack_cpu: the same contract for host arrays (no alignment asked), by the host, with m and t by
+ * value.  It checks the whole plan first: a plan that is not well-formed returns QGCM_E_ARG with nothing
+ * written.
+ *
+ * qgcm_udp_send_packed: qgcm_udp_send_plan for a packed batch: one message per train with ONE iovec,
+ * packed[off .. off + count * seg_len), msg_name addrs[peer], and for count > 1 a UDP_SEGMENT control message of
+ * seg_len; in sendmmsg batches of at most 1024 messages.  The whole table is checked before anything is sent;
+ * any violation returns -1 with nothing sent: off + count * seg_len > packed_len (so a train that did not fit,
+ * off = 0xffffffff, fails), count outside [1, 1024], peer >= n_addrs, a seg_len of 0, or above 65535 in a train of
+ * more than one.  The fallback to single datagrams (cut from the packed bytes), the sticky ENOPROTOOPT /
+ * EOPNOTSUPP rule, QGCM_UDP_GSO=0, stats and the return value are those of qgcm_udp_send_plan.
+ *
+ * qgcm_route_chain_seal_packed_host: qgcm_route_chain_seal_host with the copy back replaced.  Chunks,
+ * serialisation and the order of resolve, chain and Tx accounting are that call's.  Per chunk the chunk's d_lens
+ * and d_peer are planned on the device under `limits` (as qgcm_send_plan; always the device planner: the arrays
+ * are already there) and its trains are packed into an area the context owns (cn * round16(stride) bytes, grown
+ * on demand: the device pack always fits); then the counts come down.  If the chunk's bytes do not fit behind
+ * the fill position of h_out, the call returns QGCM_E_NOMEM before that chunk is accounted or copied: the
+ * caller's input is whole and the call can be repeated from packet out[0] on.  Otherwise the chunk is accounted
+ * and appended: its bytes to h_out (16-B steps), its table to h_ptrains (n entries; `off` rebased by the fill
+ * position) and, if h_order is not NULL, its order[0..m) to h_order (n entries; rebased by the chunk's first
+ * slot), so that h_order names the slot of every packed datagram in table order.  Trains never span a chunk:
+ * for a batch of one chunk (n <= 65536 and n * stride <= 256 MiB) the table is exactly qgcm_send_plan_cpu +
+ * qgcm_train_pack_cpu of qgcm_route_chain_seal_host's output.  h_arena is read and never written.  h_peer,
+ * h_status, h_lens and the return value are those of qgcm_route_chain_seal_host.  out = {packets fully
+ * processed, trains written, bytes of h_out used, datagrams in those trains}, written on success and on
+ * QGCM_E_NOMEM.  out_cap above 2^32 - 16 counts as 2^32 - 16. */
+typedef struct qgcm_ptrain { uint32_t off, count, peer, seg_len; } qgcm_ptrain;
+uint64_t qgcm_train_pack_work(uint32_t n);
+int qgcm_train_pack(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_order,
+                    const qgcm_train *d_trains, const uint32_t *d_plan_counts, uint8_t *d_packed, uint64_t packed_cap,
+                    qgcm_ptrain *d_ptrains, uint64_t *d_pcounts, void *d_work, void *stream);
+int qgcm_train_pack_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *order, uint32_t m,
+                        const qgcm_train *trains, uint32_t t, uint8_t *packed, uint64_t packed_cap,
+                        qgcm_ptrain *ptrains, uint64_t pcounts[2]);
+int qgcm_udp_send_packed(int fd, const uint8_t *packed, uint64_t packed_len, const qgcm_ptrain *ptrains,
+                         uint32_t n_trains, const qgcm_peer_addr *addrs, uint32_t n_addrs, uint64_t stats[3]);
+int qgcm_route_chain_seal_packed_host(qgcm_ctx *ctx, const uint8_t *h_arena, uint64_t stride, uint32_t n,
+                                      uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins,
+                                      const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
+                                      uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order,
+                                      uint64_t out[4]);
 
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19

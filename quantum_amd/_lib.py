@@ -46,6 +46,8 @@ EXPORTS = (
     "qgcm_route_open_gro_host", "qgcm_route_chain_open_gro_host",
     "qgcm_deliver_pack_work", "qgcm_deliver_pack", "qgcm_deliver_pack_cpu", "qgcm_tun_write_packed",
     "qgcm_route_chain_open_packed_host", "qgcm_route_chain_open_gro_packed_host",
+    "qgcm_train_pack_work", "qgcm_train_pack", "qgcm_train_pack_cpu", "qgcm_udp_send_packed",
+    "qgcm_route_chain_seal_packed_host",
 )
 
 QGCM_OK = 0
@@ -124,6 +126,12 @@ class PackRec(C.Structure):
     """qgcm_pack_rec: {off (0xffffffff: the record did not fit), len, slot, peer} -- 16 bytes."""
 
     _fields_ = [("off", C.c_uint32), ("len", C.c_uint32), ("slot", C.c_uint32), ("peer", C.c_uint32)]
+
+
+class PTrain(C.Structure):
+    """qgcm_ptrain: {off (0xffffffff: the train did not fit, or is void), count, peer, seg_len} -- 16 bytes."""
+
+    _fields_ = [("off", C.c_uint32), ("count", C.c_uint32), ("peer", C.c_uint32), ("seg_len", C.c_uint32)]
 
 
 _lib: C.CDLL | None = None
@@ -268,6 +276,13 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_tun_write_packed.argtypes = [C.c_int, vp, u64, vp, u32]
         L.qgcm_route_chain_open_packed_host.argtypes = [vp, vp, u64, u32, vp, u32, vp, vp, vp, u64, vp, vp]
         L.qgcm_route_chain_open_gro_packed_host.argtypes = [vp, vp, u64, vp, u32, u64, u32, vp, u32, vp, vp, vp, u64, vp, vp]
+    if hasattr(L, "qgcm_train_pack"):  # (older builds loaded by the A/B tools lack the train pack)
+        L.qgcm_train_pack_work.argtypes = [u32]
+        L.qgcm_train_pack_work.restype = u64
+        L.qgcm_train_pack.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, vp]
+        L.qgcm_train_pack_cpu.argtypes = [vp, u64, u32, vp, u32, vp, u32, vp, u64, vp, vp]
+        L.qgcm_udp_send_packed.argtypes = [C.c_int, vp, u64, vp, u32, vp, u32, vp]
+        L.qgcm_route_chain_seal_packed_host.argtypes = [vp, vp, u64, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

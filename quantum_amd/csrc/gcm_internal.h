@@ -397,6 +397,14 @@ uint64_t deliver_pack_work_bytes(uint32_t n);
 hipError_t launch_deliver_pack(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens, const uint32_t *peer,
                                const uint8_t *status, uint8_t *packed, uint64_t packed_cap, qgcm_pack_rec *recs,
                                uint64_t *counts, void *work, hipStream_t s);
+// The trains of a plan packed back to back (train_kernels.hip; include/qgcm.h "planned trains packed on routed
+// batches"): tile sums, spine, emit and the copy on s (the 16-byte path when stride and arena allow it, else the
+// dword path); m and t are read from plan_counts on the device; work: train_pack_work_bytes(n) bytes, 16-B
+// aligned; the caller has checked the arguments.  n == 0 writes pcounts = {0, 0} and launches nothing.
+uint64_t train_pack_work_bytes(uint32_t n);
+hipError_t launch_train_pack(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *order,
+                             const qgcm_train *trains, const uint32_t *plan_counts, uint8_t *packed, uint64_t packed_cap,
+                             qgcm_ptrain *ptrains, uint64_t *pcounts, void *work, hipStream_t s);
 // qgcm_send_plan_host plans on the device from this many packets on (QGCM_PLAN_DEVICE_MIN at qgcm_create): the
 // measured crossover -- 181 against 186 us at 65536, 319 against 993 us at 262144
 constexpr uint32_t kPlanDeviceMin = 65536;

@@ -21,6 +21,7 @@
 #include "gro_core.h"
 #include "pack_core.h"
 #include "send_plan_core.h"
+#include "train_core.h"
 
 namespace qgcm {
 
@@ -61,6 +62,11 @@ struct RouteState {
     // pipe_mu, on `stream`)
     uint8_t *d_pack = nullptr;
     size_t pack_cap = 0;
+
+    // the packed outgoing pipeline: a chunk's plan, its packed table, counts, work areas and packed bytes on the
+    // device (under pipe_mu, on `stream`)
+    uint8_t *d_train = nullptr;
+    size_t train_cap = 0;
 };
 
 RouteState *route_state_create() {
@@ -80,6 +86,7 @@ void route_state_destroy(RouteState *r) {
     hipFree(r->d_plan);
     hipFree(r->d_gro);
     hipFree(r->d_pack);
+    hipFree(r->d_train);
     if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
@@ -296,13 +303,108 @@ void pack_rebase(PackOut &pk, uint32_t c0, uint32_t cn) {
     pk.out[2] = pk.fill;
 }
 
+// The copy back of the packed outgoing pipeline (include/qgcm.h "planned trains packed on routed batches"): where
+// the caller's packed area, table and order are, and how far they are filled.
+struct TrainOut {
+    uint8_t *h_out;
+    uint64_t out_cap;  // at most kTrainMaxCap: `off` is 32 bits
+    qgcm_ptrain *h_ptrains;
+    uint32_t *h_order;  // may be NULL
+    uint64_t *out;      // {packets fully processed, trains written, bytes of h_out used, datagrams in those trains}
+    qgcm_plan_limits lim;
+    uint64_t fill = 0, t = 0, m = 0;
+    // the device area of a chunk
+    qgcm_train *d_trains = nullptr;
+    qgcm_ptrain *d_ptrains = nullptr;
+    uint32_t *d_order = nullptr, *d_counts = nullptr;
+    uint64_t *d_pcounts = nullptr;
+    void *d_plan_work = nullptr, *d_work = nullptr;
+    uint8_t *d_packed = nullptr;
+    uint64_t plan_work_bytes = 0;
+    uint32_t h_counts[2] = {0, 0};
+    uint64_t h_pcounts[2] = {0, 0};
+};
+
+inline uint64_t train_area_bytes(uint32_t cn, uint64_t stride) {
+    return std::min<uint64_t>((uint64_t)cn * ((stride + 15) & ~(uint64_t)15), kTrainMaxCap);
+}
+
+// trains and ptrains (16-B aligned first), order, the plan's counts, pcounts (8-B aligned), the planner's work area
+// (256-B aligned), the scan's, the packed bytes (16-B aligned)
+bool train_grow(RouteState *r, TrainOut &tk, uint32_t max_cn, uint64_t stride) {
+    tk.plan_work_bytes = send_plan_work_bytes(max_cn);
+    const size_t o_ptrains = 16ull * max_cn, o_order = o_ptrains + 16ull * max_cn, o_counts = o_order + 4ull * max_cn,
+                 o_pcounts = (o_counts + 8 + 15) & ~(size_t)15, o_plan_work = (o_pcounts + 16 + 255) & ~(size_t)255,
+                 o_work = (o_plan_work + (size_t)tk.plan_work_bytes + 255) & ~(size_t)255,
+                 o_packed = o_work + (size_t)train_pack_work_bytes(max_cn);
+    if (!grow(r->d_train, r->train_cap, o_packed + std::max<size_t>((size_t)train_area_bytes(max_cn, stride), 16))) return false;
+    tk.d_trains = reinterpret_cast<qgcm_train *>(r->d_train);
+    tk.d_ptrains = reinterpret_cast<qgcm_ptrain *>(r->d_train + o_ptrains);
+    tk.d_order = reinterpret_cast<uint32_t *>(r->d_train + o_order);
+    tk.d_counts = reinterpret_cast<uint32_t *>(r->d_train + o_counts);
+    tk.d_pcounts = reinterpret_cast<uint64_t *>(r->d_train + o_pcounts);
+    tk.d_plan_work = r->d_train + o_plan_work;
+    tk.d_work = r->d_train + o_work;
+    tk.d_packed = r->d_train + o_packed;
+    return true;
+}
+
+// A chunk's sealed datagrams planned and packed on the device, behind its chain on s; the counts of both come
+// down.  QGCM_E_NOMEM (out written) when the chunk's bytes do not fit behind the fill position: nothing of it is
+// accounted or copied.
+int train_chunk(TrainOut &tk, uint32_t max_keys, const uint8_t *d_arena, uint64_t stride, uint32_t c0, uint32_t cn,
+                const uint32_t *d_lens, const uint32_t *d_peer, hipStream_t s) {
+    if (launch_send_plan(cn, max_keys, d_lens, d_peer, tk.lim, tk.d_order, tk.d_trains, tk.d_counts, tk.d_plan_work,
+                         tk.plan_work_bytes, s) != hipSuccess ||
+        launch_train_pack(d_arena, stride, cn, tk.d_order, tk.d_trains, tk.d_counts, tk.d_packed, train_area_bytes(cn, stride),
+                          tk.d_ptrains, tk.d_pcounts, tk.d_work, s) != hipSuccess ||
+        hipMemcpyAsync(tk.h_counts, tk.d_counts, 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(tk.h_pcounts, tk.d_pcounts, 16, hipMemcpyDeviceToHost, s) != hipSuccess)
+        return QGCM_E_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess || tk.h_counts[0] > cn || tk.h_counts[1] > tk.h_counts[0] ||
+        tk.h_pcounts[0] != tk.h_counts[1])
+        return QGCM_E_HIP;
+    tk.out[0] = c0;
+    tk.out[1] = tk.t;
+    tk.out[2] = tk.fill;
+    tk.out[3] = tk.m;
+    // a chunk whose trains did not all fit the device area (slots of more than 4 GiB) cannot be sent
+    if (tk.h_pcounts[1] > train_area_bytes(cn, stride) || tk.fill + tk.h_pcounts[1] > tk.out_cap) return QGCM_E_NOMEM;
+    return QGCM_OK;
+}
+
+// ... and, once the chunk is accounted, its bytes, table and order appended to the caller's
+bool train_copy_back(TrainOut &tk, hipStream_t s) {
+    const uint64_t m = tk.h_counts[0], t = tk.h_counts[1], bytes = tk.h_pcounts[1];
+    return (!bytes || hipMemcpyAsync(tk.h_out + tk.fill, tk.d_packed, (size_t)bytes, hipMemcpyDeviceToHost, s) == hipSuccess) &&
+           (!t || hipMemcpyAsync(tk.h_ptrains + tk.t, tk.d_ptrains, 16ull * t, hipMemcpyDeviceToHost, s) == hipSuccess) &&
+           (!m || !tk.h_order || hipMemcpyAsync(tk.h_order + tk.m, tk.d_order, 4ull * m, hipMemcpyDeviceToHost, s) == hipSuccess);
+}
+
+// ... and, once they have arrived, rebased: `off` by the fill position, the order by the chunk's first slot
+void train_rebase(TrainOut &tk, uint32_t c0, uint32_t cn) {
+    const uint64_t m = tk.h_counts[0], t = tk.h_counts[1];
+    if (tk.fill)
+        for (uint64_t j = tk.t; j < tk.t + t; ++j) tk.h_ptrains[j].off += (uint32_t)tk.fill;
+    if (c0 && tk.h_order)
+        for (uint64_t p = tk.m; p < tk.m + m; ++p) tk.h_order[p] += c0;
+    tk.t += t;
+    tk.m += m;
+    tk.fill += tk.h_pcounts[1];
+    tk.out[0] = (uint64_t)c0 + cn;
+    tk.out[1] = tk.t;
+    tk.out[2] = tk.fill;
+    tk.out[3] = tk.m;
+}
+
 // Outgoing.pipeline / Incoming.pipeline for a batch in host memory: chunks of at most kRouteChunk packets,
 // copy in -> resolve -> seal or open (chain: the plugin chain under the node's `plugins`) -> account -> copy
 // back, on one stream.  With `pk` (the incoming chain only) the copy back is the packed one: the pack runs
 // behind the chain, its counts are waited for before the chunk is accounted, and the arena stays on the device.
+// With `tk` (the outgoing chain only) the same for the planned trains: plan and train pack run behind the chain.
 int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
                    const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status, bool chain = false,
-                   uint32_t plugins = 0, PackOut *pk = nullptr) {
+                   uint32_t plugins = 0, PackOut *pk = nullptr, TrainOut *tk = nullptr) {
     if (!ctx) return QGCM_E_ARG;
     RouteState *r = ctx_route(ctx);
     if ((stride & 3) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
@@ -332,6 +434,7 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
                  side = chain ? o_work + QGCM_CHAIN_WORK(chunk) : o_stat + chunk;
     if (!grow(r->d_arena, r->arena_cap, (size_t)chunk * stride) || !grow(r->d_side, r->side_cap, side)) return QGCM_E_NOMEM;
     if (pk && !pack_grow(r, *pk, chunk, stride)) return QGCM_E_NOMEM;
+    if (tk && !train_grow(r, *tk, chunk, stride)) return QGCM_E_NOMEM;
     r->h_stat.resize(chunk);
     qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
     uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
@@ -352,6 +455,7 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
             rc = run_chain(ctx, seal, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, nonces, d_stat, d_bytes,
                            r->d_side + o_work, s);
             if (rc == QGCM_OK && pk) rc = pack_chunk(*pk, r->d_arena, stride, c0, cn, d_lens, d_peer, d_stat, s);
+            if (rc == QGCM_OK && tk) rc = train_chunk(*tk, ctx_max_keys(ctx), r->d_arena, stride, c0, cn, d_lens, d_peer, s);
             if (rc == QGCM_OK) rc = account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
         } else if (rc == QGCM_OK) {
             rc = seal ? qgcm_seal_batch(ctx, r->d_arena, d_descs, cn, nonces, 4, d_stat, s)
@@ -359,8 +463,9 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
             if (rc == QGCM_OK) rc = qgcm_route_account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, d_descs, d_stat, s);
         }
         if (rc == QGCM_OK &&
-            ((pk ? !pack_copy_back(*pk, s)
-                 : hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+            ((pk   ? !pack_copy_back(*pk, s)
+              : tk ? !train_copy_back(*tk, s)
+                   : hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess) ||
              hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
              hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
              // the chain's lengths are final on the device (the tables of include/qgcm.h)
@@ -369,6 +474,7 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
         if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
         if (rc != QGCM_OK) return rc;
         if (pk) pack_rebase(*pk, c0, cn);
+        if (tk) train_rebase(*tk, c0, cn);
         for (uint32_t i = 0; i < cn; ++i) {
             const bool ok = r->h_stat[i] == 1;
             if (chain) {
@@ -761,6 +867,36 @@ int qgcm_route_chain_open_gro_packed_host(qgcm_ctx *ctx, const uint8_t *h_packed
     PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), h_recs, out};
     return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, nullptr, stride, n, h_lens, h_peer, h_status, true,
                               plugins, &pk);
+}
+
+uint64_t qgcm_train_pack_work(uint32_t n) { return train_pack_work_bytes(n); }
+
+int qgcm_train_pack(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_order,
+                    const qgcm_train *d_trains, const uint32_t *d_plan_counts, uint8_t *d_packed, uint64_t packed_cap,
+                    qgcm_ptrain *d_ptrains, uint64_t *d_pcounts, void *d_work, void *stream) {
+    if (!ctx || n > QGCM_MAX_BATCH || (stride & 3) || packed_cap > kTrainMaxCap || !d_pcounts) return QGCM_E_ARG;
+    if (n && (!d_arena || !d_order || !d_trains || !d_plan_counts || !d_packed || !d_ptrains || !d_work || stride == 0))
+        return QGCM_E_ARG;
+    if (((uintptr_t)d_arena & 3) || ((uintptr_t)d_order & 3) || ((uintptr_t)d_trains & 15) || ((uintptr_t)d_plan_counts & 3) ||
+        ((uintptr_t)d_packed & 15) || ((uintptr_t)d_ptrains & 15) || ((uintptr_t)d_pcounts & 7) || ((uintptr_t)d_work & 15))
+        return QGCM_E_ARG;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    return hip_rc(launch_train_pack(d_arena, stride, n, d_order, d_trains, d_plan_counts, d_packed, packed_cap, d_ptrains,
+                                    d_pcounts, d_work, (hipStream_t)stream));
+}
+
+int qgcm_route_chain_seal_packed_host(qgcm_ctx *ctx, const uint8_t *h_arena, uint64_t stride, uint32_t n,
+                                      uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins,
+                                      const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
+                                      uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order,
+                                      uint64_t out[4]) {
+    if (!out || (n && (!h_out || !h_ptrains))) return QGCM_E_ARG;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    TrainOut tk{h_out, std::min<uint64_t>(out_cap, kTrainMaxCap), h_ptrains, h_order, out};
+    if (!plan_limits_resolve(limits, &tk.lim)) return QGCM_E_ARG;
+    // the arena is only read: with `tk` the copy back never names it
+    return run_route_host(ctx, true, const_cast<uint8_t *>(h_arena), stride, n, h_lens, h_nonces, h_peer, h_status, true,
+                          plugins, nullptr, &tk);
 }
 
 int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]) {

@@ -23,6 +23,7 @@
 #include "../../include/qgcm.h"
 #include "gro_core.h"
 #include "pack_core.h"
+#include "train_core.h"
 
 #ifndef UDP_SEGMENT
 #define UDP_SEGMENT 103  // linux/udp.h, Linux 4.18
@@ -364,6 +365,141 @@ int qgcm_udp_send_plan(int fd, const uint8_t *arena, uint64_t stride, uint32_t n
     return finish(false);
 }
 
+// socket/udp.go:43-47 for a planned batch whose trains the GPU has packed (qgcm_train_pack, or
+// qgcm_route_chain_seal_packed_host): qgcm_udp_send_plan with every train one contiguous stretch of the packed
+// area, so a message is one iovec whatever its count.  The contract is in include/qgcm.h.
+int qgcm_udp_send_packed(int fd, const uint8_t *packed, uint64_t packed_len, const qgcm_ptrain *ptrains,
+                         uint32_t n_trains, const qgcm_peer_addr *addrs, uint32_t n_addrs, uint64_t stats[3]) {
+    if (stats) stats[0] = stats[1] = stats[2] = 0;
+    if (fd < 0 || (n_trains && (!packed || !ptrains)) || (n_addrs && !addrs)) return -1;
+    // the whole table before the first byte leaves
+    if (!qgcm::train_table_ok(ptrains, n_trains, packed_len, n_addrs)) return -1;
+    const char *gso_env = getenv("QGCM_UDP_GSO");
+    bool gso = !(gso_env && !strcmp(gso_env, "0"));
+
+    struct SegCtl {
+        alignas(cmsghdr) char buf[CMSG_SPACE(sizeof(uint16_t))];
+    };
+    std::vector<mmsghdr> msgs(kVlen);
+    std::vector<iovec> iov(kVlen);  // one a message
+    std::vector<sockaddr_in> dst(kVlen);
+    std::vector<SegCtl> ctl(kVlen);
+    std::vector<uint32_t> msg_train(kVlen);  // the train of each queued message
+    std::vector<uint32_t> msg_dgrams(kVlen); // the datagrams it carries
+    uint64_t sent = 0, n_msgs = 0, n_seg = 0, n_fell = 0;
+    auto finish = [&](bool failed) {
+        if (stats) {
+            stats[0] = n_msgs;
+            stats[1] = n_seg;
+            stats[2] = n_fell;
+        }
+        return failed && sent == 0 ? -1 : (int)sent;
+    };
+    // datagram i of a train, cut from the packed bytes
+    auto cut_iov = [&](const qgcm_ptrain &tr, uint32_t i, uint32_t count) {
+        return iovec{const_cast<uint8_t *>(packed) + tr.off + (uint64_t)i * tr.seg_len, (size_t)count * tr.seg_len};
+    };
+    auto set_dst = [&](sockaddr_in *d, uint32_t peer) {
+        memset(d, 0, sizeof *d);
+        d->sin_family = AF_INET;
+        d->sin_addr.s_addr = addrs[peer].ip;  // network byte order already
+        d->sin_port = addrs[peer].port;
+    };
+    // a train as `count` plain datagrams (count <= kVlen), through buffers of its own: the segmented
+    // messages queued behind a train that fell back keep theirs; false: a send failed
+    std::vector<mmsghdr> one_msgs;
+    std::vector<iovec> one_iov;
+    sockaddr_in one_dst;
+    auto send_singles = [&](const qgcm_ptrain &tr) {
+        one_msgs.resize(kVlen);
+        one_iov.resize(kVlen);
+        set_dst(&one_dst, tr.peer);
+        for (uint32_t i = 0; i < tr.count; ++i) {
+            one_iov[i] = cut_iov(tr, i, 1);
+            one_msgs[i] = mmsghdr{};
+            one_msgs[i].msg_hdr.msg_name = &one_dst;
+            one_msgs[i].msg_hdr.msg_namelen = sizeof one_dst;
+            one_msgs[i].msg_hdr.msg_iov = &one_iov[i];
+            one_msgs[i].msg_hdr.msg_iovlen = 1;
+        }
+        for (uint32_t done = 0; done < tr.count;) {
+            const int r = sendmmsg(fd, one_msgs.data() + done, tr.count - done, 0);
+            if (r < 0) {
+                if (errno == EINTR) continue;
+                return false;
+            }
+            done += (uint32_t)r;
+            sent += (uint64_t)r;
+            n_msgs += (uint64_t)r;
+        }
+        return true;
+    };
+
+    uint32_t next = 0;  // the next train to queue
+    while (next < n_trains) {
+        unsigned k = 0;  // messages queued; an empty queue takes any train
+        for (; next < n_trains; ++next) {
+            const qgcm_ptrain &tr = ptrains[next];
+            // a segmented train is one message over the train's bytes; a train of one, and every train under
+            // QGCM_UDP_GSO=0, is `count` plain messages
+            const bool seg = gso && tr.count > 1;
+            const unsigned n_new = seg ? 1u : tr.count;
+            if (k + n_new > kVlen) break;
+            for (unsigned i = 0; i < n_new; ++i, ++k) {
+                iov[k] = seg ? cut_iov(tr, 0, tr.count) : cut_iov(tr, i, 1);
+                set_dst(&dst[k], tr.peer);
+                msgs[k] = mmsghdr{};
+                msghdr &h = msgs[k].msg_hdr;
+                h.msg_name = &dst[k];
+                h.msg_namelen = sizeof dst[k];
+                h.msg_iov = &iov[k];
+                h.msg_iovlen = 1;
+                if (seg) {
+                    memset(ctl[k].buf, 0, sizeof ctl[k].buf);
+                    h.msg_control = ctl[k].buf;
+                    h.msg_controllen = sizeof ctl[k].buf;
+                    cmsghdr *cm = CMSG_FIRSTHDR(&h);
+                    cm->cmsg_level = SOL_UDP;
+                    cm->cmsg_type = UDP_SEGMENT;
+                    cm->cmsg_len = CMSG_LEN(sizeof(uint16_t));
+                    const uint16_t seg_len = (uint16_t)tr.seg_len;
+                    memcpy(CMSG_DATA(cm), &seg_len, sizeof seg_len);
+                }
+                msg_train[k] = next;
+                msg_dgrams[k] = seg ? tr.count : 1u;
+            }
+        }
+        for (unsigned done = 0; done < k;) {
+            const int r = sendmmsg(fd, msgs.data() + done, k - done, 0);
+            if (r >= 0) {
+                for (int i = 0; i < r; ++i) {
+                    sent += msg_dgrams[done + i];
+                    n_seg += msg_dgrams[done + i] > 1;
+                }
+                n_msgs += (uint64_t)r;
+                done += (unsigned)r;
+                continue;
+            }
+            if (errno == EINTR) continue;
+            // msgs[done] is the one that failed
+            const bool unsupported = errno == ENOPROTOOPT || errno == EOPNOTSUPP;
+            const bool refused = unsupported || errno == EINVAL || errno == EIO || errno == EMSGSIZE;
+            if (msg_dgrams[done] == 1 || !refused) return finish(true);
+            ++n_fell;
+            if (!send_singles(ptrains[msg_train[done]])) return finish(true);
+            ++done;
+            if (unsupported) {
+                // this socket takes no UDP_SEGMENT at all: the trains queued behind this one, and the rest
+                // of the call, go unsegmented without asking again
+                gso = false;
+                if (done < k) next = msg_train[done];
+                break;
+            }
+        }
+    }
+    return finish(false);
+}
+
 // socket/udp.go:49-70 plus the UDP_GRO option: the kernel then hands a train of equal-length datagrams of one
 // sender back as one buffer (qgcm_udp_recv_gro).
 int qgcm_udp_gro(int fd, int on) {
@@ -445,6 +581,20 @@ int qgcm_deliver_pack_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, con
     if (n > QGCM_MAX_BATCH || (stride & 3) || packed_cap > qgcm::kPackMaxCap || !counts) return QGCM_E_ARG;
     if (n && (!arena || !lens || !peer || !packed || !recs || stride == 0)) return QGCM_E_ARG;
     qgcm::deliver_pack_cpu(arena, stride, n, lens, peer, status, packed, packed_cap, recs, counts);
+    return QGCM_OK;
+}
+
+// The trains of a planned batch packed back to back by the host (train_core.h; the contract of qgcm_train_pack,
+// no alignment asked, the plan checked whole first): what a worker on qgcm_route_chain_seal_host hands to
+// qgcm_udp_send_packed.
+int qgcm_train_pack_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *order, uint32_t m,
+                        const qgcm_train *trains, uint32_t t, uint8_t *packed, uint64_t packed_cap,
+                        qgcm_ptrain *ptrains, uint64_t pcounts[2]) {
+    if (n > QGCM_MAX_BATCH || (stride & 3) || packed_cap > qgcm::kTrainMaxCap || !pcounts) return QGCM_E_ARG;
+    if (n && (!arena || !order || !trains || !packed || !ptrains || stride == 0)) return QGCM_E_ARG;
+    if ((m && !order) || (t && (!trains || !ptrains || !arena || !packed))) return QGCM_E_ARG;
+    if (!qgcm::train_plan_ok(stride, n, order, m, trains, t)) return QGCM_E_ARG;
+    qgcm::train_pack_cpu(arena, stride, order, trains, t, packed, packed_cap, ptrains, pcounts);
     return QGCM_OK;
 }
 

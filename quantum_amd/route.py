@@ -477,3 +477,74 @@ def route_chain_open_gro_packed_host(ctx, packed, packed_len: int, bufs, stride:
                                                           out_buf.ctypes.data, out_buf.size, recs.ctypes.data,
                                                           out.ctypes.data)
     return _packed_result(rc, "qgcm_route_chain_open_gro_packed_host", recs, out)
+
+
+TRAIN_NO_ROOM = 0xFFFFFFFF  # `off` of a train that did not fit below packed_cap, or is void
+
+
+def train_pack_work(n: int, device="cuda"):
+    """A work area for a train_pack call of n packets (qgcm_train_pack_work(n) bytes; torch allocations are
+    16-B aligned)."""
+    import torch
+
+    return torch.empty(int(_lib.lib().qgcm_train_pack_work(n)), dtype=torch.uint8, device=device)
+
+
+def train_pack(ctx, arena, stride: int, n: int, order, trains, plan_counts, packed, packed_cap: int, ptrains, pcounts,
+               work, stream=None) -> None:
+    """qgcm_train_pack after send_plan on the same stream (no synchronisation in between: m and t are read on the
+    device): `order` / `trains` / `plan_counts` as send_plan wrote them, `packed` uint8 (16-B aligned), `ptrains`
+    int32 (4 n: off, count, peer, seg_len per train), `pcounts` int64 (2: t, bytes), `work` from
+    train_pack_work(n)."""
+    _lib.check(_lib.lib().qgcm_train_pack(ctx.handle, _ptr(arena), stride, n, _ptr(order), _ptr(trains), _ptr(plan_counts),
+                                          _ptr(packed), packed_cap, _ptr(ptrains), _ptr(pcounts), _ptr(work),
+                                          _stream_handle(stream)), "qgcm_train_pack")
+
+
+def train_pack_cpu(arena, stride: int, n: int, order, trains, packed, ptrains=None):
+    """qgcm_train_pack_cpu over numpy arrays: `arena` / `packed` uint8 (packed_cap = packed.size), `order` uint32
+    (m), `trains` uint32 (t, 4) -> (ptrains[:t] a (t, 4) uint32 array of off, count, peer, seg_len; bytes, the full
+    need).  `packed` is written in place.  Raises for a plan that is not well-formed."""
+    import numpy as np
+
+    if ptrains is None:
+        ptrains = np.zeros((max(1, len(trains)), 4), np.uint32)
+    pcounts = np.zeros(2, np.uint64)
+    _lib.check(_lib.lib().qgcm_train_pack_cpu(arena.ctypes.data, stride, n, order.ctypes.data, len(order),
+                                              trains.ctypes.data, len(trains), packed.ctypes.data, packed.size,
+                                              ptrains.ctypes.data, pcounts.ctypes.data), "qgcm_train_pack_cpu")
+    return ptrains[:int(pcounts[0])], int(pcounts[1])
+
+
+def udp_send_packed(fd: int, packed, packed_len: int, ptrains, addrs: C.Array, n_addrs: int, stats=None) -> int:
+    """qgcm_udp_send_packed: one message per train of `ptrains` (numpy uint32 (t, 4)), one iovec each, UDP_SEGMENT
+    for count > 1; `stats` a numpy uint64 array of 3 or None.  Returns the number of datagrams sent or -1."""
+    return _lib.lib().qgcm_udp_send_packed(fd, packed.ctypes.data, packed_len, ptrains.ctypes.data, len(ptrains),
+                                           C.addressof(addrs), n_addrs, None if stats is None else stats.ctypes.data)
+
+
+def route_chain_seal_packed_host(ctx, arena_ptr: int, stride: int, n: int, lens, nonces, plugins: int, peer, status,
+                                 out_buf, limits=None, ptrains=None, order=None):
+    """qgcm_route_chain_seal_packed_host: route_chain_seal_host whose sealed datagrams come back planned and packed
+    into `out_buf` (a numpy uint8 array) -> (rc, ptrains[:t], order[:m], out): rc the number of drops or
+    QGCM_E_NOMEM (out_buf too small: out[0] packets are done, repeat from there), ptrains a (t, 4) uint32 array,
+    order the slot of every packed datagram in table order, out = {packets fully processed, trains written, bytes
+    of out_buf used, datagrams in those trains}."""
+    import numpy as np
+
+    from .batch import GENERATE
+
+    if ptrains is None:
+        ptrains = np.zeros((max(1, n), 4), np.uint32)
+    if order is None:
+        order = np.zeros(max(1, n), np.uint32)
+    out = np.zeros(4, np.uint64)
+    np_ = _lib.NONCES_GENERATE if nonces is GENERATE else nonces
+    rc = _lib.lib().qgcm_route_chain_seal_packed_host(ctx.handle, arena_ptr, stride, n, lens.ctypes.data, np_, plugins,
+                                                      _limits_ptr(limits), peer.ctypes.data,
+                                                      None if status is None else status.ctypes.data,
+                                                      out_buf.ctypes.data, out_buf.size, ptrains.ctypes.data,
+                                                      order.ctypes.data, out.ctypes.data)
+    if rc < 0 and rc != _lib.QGCM_E_NOMEM:
+        _lib.check(rc, "qgcm_route_chain_seal_packed_host")
+    return rc, ptrains[:int(out[1])], order[:int(out[3])], out
