@@ -889,6 +889,71 @@ int qgcm_route_chain_seal_packed_host(qgcm_ctx *ctx, const uint8_t *h_arena, uin
                                       uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order,
                                       uint64_t out[4]);
 
+/* ---- outgoing frames packed on routed batches: the TUN read and the copy up at their own size ---- */
+/* qgcm_tun_read_slots reads every TUN packet into a slot of `stride` bytes and the outgoing pipelines copy whole
+ * slots up.  Here the read lays the packets back to back, a table names them, and one launch on the device puts
+ * them into slots and resolves them -- the mirror of the packed copy back, so that the outgoing pipeline crosses
+ * PCIe at its own size in both directions.
+ *
+ * Frame table: frame i is packed[off_i, off_i + len_i) and belongs to slot i.  A frame is valid when off is a
+ * multiple of 16 and off + len <= packed_len (computed in 64 bits); any other frame is void.
+ *
+ * qgcm_frames_resolve: device arrays, asynchronous on stream, one launch.  For a valid frame it leaves exactly
+ * what an unpack followed by qgcm_resolve_outgoing leaves: Raw[4 : 4 + min(len, stride - 4)) of slot i takes the
+ * frame's bytes; d_lens[i] = len (the true length, also when the bytes were clamped); own_ip into Raw[0:4] on a
+ * hit, while on a miss the four bytes keep their value; d_peer[i] and d_descs[i] as qgcm_resolve_outgoing
+ * documents them, its divergences included (len < 20 and 4 + len + 28 > stride are misses).  Every other byte of
+ * the arena keeps its value: the slot's tail, and what lies behind a short frame.  For a void frame d_lens[i] = 0,
+ * d_peer[i] = QGCM_NO_PEER, d_descs[i] = {i * stride, 0, QGCM_NO_PEER} and the slot is untouched.  The call is
+ * memory-safe on any table: it reads nothing behind the 16-byte boundary after packed_len and nothing outside
+ * the arena's n * stride bytes.  d_packed and d_descs 16-B aligned, the d_packed allocation rounded up to 16 B;
+ * d_frames 8-B aligned; d_lens, d_peer and d_arena 4-B aligned; stride a nonzero multiple of 4 and at least 8 (a
+ * stride that is a multiple of 16 under a 16-B-aligned arena takes the 16-byte path, anything else the dword
+ * path).  n == 0: QGCM_OK, nothing launched.  n > QGCM_MAX_BATCH, a bad stride, a NULL or misaligned pointer, or
+ * a call before qgcm_routes_set: QGCM_E_ARG, nothing launched.  The route table is taken under the context's
+ * route lock as qgcm_resolve_outgoing takes it.
+ *
+ * qgcm_frames_unpack_cpu: the unpack half for host arrays (no alignment asked; stride as above), for workers
+ * without the device path, and the yardstick of the pipeline below.  It checks the table first: a frame that is
+ * not valid returns QGCM_E_ARG with nothing written.  Otherwise lens[i] = len and Raw[4 : 4 + min(len,
+ * stride - 4)) of slot i for every frame, nothing else.
+ *
+ * qgcm_tun_read_packed: qgcm_tun_read_slots for a packed area.  It waits up to timeout_ms for the first packet,
+ * then drains what the queue holds with one preadv2(RWF_NOWAIT) per packet straight into `packed` at the fill
+ * position rounded up to 16, and writes one qgcm_frame per packet.  It stops before a read when fewer than 65536
+ * bytes of room are left -- no frame is ever truncated -- and at max_n.  Where RWF_NOWAIT is refused, or with
+ * QGCM_TUN_URING=-1, it polls and reads as qgcm_tun_read_slots does; with QGCM_TUN_URING=1 it still uses preadv2:
+ * a ring submission names every destination before a length is known, so it cannot lay frames back to back.
+ * Returns the count, 0 on timeout, or -1 (also for a NULL array or a packed_cap below 65536).  out (may be NULL)
+ * = {frames, bytes used = the end of the last frame}.
+ *
+ * qgcm_route_chain_seal_frames_host: qgcm_route_chain_seal_packed_host with the copy-in replaced.  The whole
+ * table is checked first: every frame valid and the offsets ascending without overlap (off_i + len_i <=
+ * off_{i+1}), else QGCM_E_ARG with nothing launched.  h_nonces n * 12 bytes or QGCM_NONCES_GENERATE; NULL is
+ * QGCM_E_ARG (no host slot exists to carry a nonce).  Chunks are that call's (at most 65536 packets and 256 MiB
+ * of slots) and fall at frame boundaries.  Per chunk only the packed bytes its frames span (from the first
+ * frame's off, a 16-B boundary, to the last frame's end) and their table entries (rebased to the span) go up;
+ * qgcm_frames_resolve puts them into the context's device arena; the chain, the plan, the train pack, the Tx
+ * accounting and the copy back follow as in that call, on the same stream and under the same pipeline lock.
+ * h_lens is output only.  h_peer, h_status, h_lens, h_out, h_ptrains, h_order, out, the return value and the Tx
+ * counters are what qgcm_route_chain_seal_packed_host gives for the arena and lengths qgcm_frames_unpack_cpu makes
+ * of the same input.  QGCM_E_NOMEM as in that call (out written); the call is then repeated with
+ * frames + out[0] and n - out[0] over the same packed area -- offsets are absolute, nothing is rebased. */
+typedef struct qgcm_frame { uint32_t off, len; } qgcm_frame;
+int qgcm_tun_read_packed(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_frame *frames,
+                         uint32_t max_n, int timeout_ms, uint64_t out[2]);
+int qgcm_frames_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len,
+                        const qgcm_frame *d_frames, uint32_t n, uint8_t *d_arena, uint64_t stride,
+                        uint32_t *d_lens, uint32_t *d_peer, qgcm_desc *d_descs, void *stream);
+int qgcm_frames_unpack_cpu(const uint8_t *packed, uint64_t packed_len, const qgcm_frame *frames,
+                           uint32_t n, uint8_t *arena, uint64_t stride, uint32_t *lens);
+int qgcm_route_chain_seal_frames_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
+                                      const qgcm_frame *frames, uint64_t stride, uint32_t n,
+                                      uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins,
+                                      const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
+                                      uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains,
+                                      uint32_t *h_order, uint64_t out[4]);
+
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19
  * packets; a descriptor batch launches the segmented kernel and then the per-wave kernel for its

@@ -48,6 +48,7 @@ EXPORTS = (
     "qgcm_route_chain_open_packed_host", "qgcm_route_chain_open_gro_packed_host",
     "qgcm_train_pack_work", "qgcm_train_pack", "qgcm_train_pack_cpu", "qgcm_udp_send_packed",
     "qgcm_route_chain_seal_packed_host",
+    "qgcm_tun_read_packed", "qgcm_frames_resolve", "qgcm_frames_unpack_cpu", "qgcm_route_chain_seal_frames_host",
 )
 
 QGCM_OK = 0
@@ -132,6 +133,12 @@ class PTrain(C.Structure):
     """qgcm_ptrain: {off (0xffffffff: the train did not fit, or is void), count, peer, seg_len} -- 16 bytes."""
 
     _fields_ = [("off", C.c_uint32), ("count", C.c_uint32), ("peer", C.c_uint32), ("seg_len", C.c_uint32)]
+
+
+class Frame(C.Structure):
+    """qgcm_frame: {off (a multiple of 16), len}: packed[off, off + len) belongs to slot i -- 8 bytes."""
+
+    _fields_ = [("off", C.c_uint32), ("len", C.c_uint32)]
 
 
 _lib: C.CDLL | None = None
@@ -283,6 +290,11 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_train_pack_cpu.argtypes = [vp, u64, u32, vp, u32, vp, u32, vp, u64, vp, vp]
         L.qgcm_udp_send_packed.argtypes = [C.c_int, vp, u64, vp, u32, vp, u32, vp]
         L.qgcm_route_chain_seal_packed_host.argtypes = [vp, vp, u64, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp]
+    if hasattr(L, "qgcm_frames_resolve"):  # (older builds loaded by the A/B tools lack the packed frames)
+        L.qgcm_tun_read_packed.argtypes = [C.c_int, vp, u64, vp, u32, C.c_int, vp]
+        L.qgcm_frames_resolve.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp]
+        L.qgcm_frames_unpack_cpu.argtypes = [vp, u64, vp, u32, vp, u64, vp]
+        L.qgcm_route_chain_seal_frames_host.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

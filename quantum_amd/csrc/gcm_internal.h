@@ -405,6 +405,25 @@ uint64_t train_pack_work_bytes(uint32_t n);
 hipError_t launch_train_pack(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *order,
                              const qgcm_train *trains, const uint32_t *plan_counts, uint8_t *packed, uint64_t packed_cap,
                              qgcm_ptrain *ptrains, uint64_t *pcounts, void *work, hipStream_t s);
+// Packed frames put into slots and resolved (frames_kernels.hip; include/qgcm.h "outgoing frames packed on
+// routed batches"): frame i of the table to Raw[4:] of slot i, then what route_resolve_kernel<outgoing> does
+// with it, one launch on s (the 16-byte path when stride and arena allow it, else the dword path).  packed is
+// 16-B aligned and readable up to the 16-B boundary behind packed_len; stride a multiple of 4, at least 8; the
+// caller has checked the arguments.
+struct FramesArgs {
+    const uint8_t *packed;
+    uint64_t packed_len;
+    const qgcm_frame *frames;  // 8-B aligned
+    uint32_t n;
+    uint8_t *arena;
+    uint64_t stride;
+    uint32_t *lens, *peer;
+    qgcm_desc *descs;          // 16-B aligned
+    const uint2 *table;
+    uint32_t cap_mask;
+    uint32_t net, mask, gateway, own_ip;
+};
+hipError_t launch_frames_resolve(const FramesArgs &a, hipStream_t s);
 // qgcm_send_plan_host plans on the device from this many packets on (QGCM_PLAN_DEVICE_MIN at qgcm_create): the
 // measured crossover -- 181 against 186 us at 65536, 319 against 993 us at 262144
 constexpr uint32_t kPlanDeviceMin = 65536;

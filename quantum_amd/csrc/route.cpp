@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/qgcm.h"
+#include "frames_core.h"
 #include "gcm_internal.h"
 #include "gro_core.h"
 #include "pack_core.h"
@@ -67,6 +68,12 @@ struct RouteState {
     // device (under pipe_mu, on `stream`)
     uint8_t *d_train = nullptr;
     size_t train_cap = 0;
+
+    // the packed-frames pipeline: a chunk's table and packed bytes on the device, the rebased table on the host
+    // (under pipe_mu, on `stream`)
+    uint8_t *d_frames = nullptr;
+    size_t frames_cap = 0;
+    std::vector<qgcm_frame> h_frames;
 };
 
 RouteState *route_state_create() {
@@ -87,6 +94,7 @@ void route_state_destroy(RouteState *r) {
     hipFree(r->d_gro);
     hipFree(r->d_pack);
     hipFree(r->d_train);
+    hipFree(r->d_frames);
     if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
@@ -125,6 +133,39 @@ int resolve(qgcm_ctx *ctx, bool outgoing, uint8_t *d_arena, uint64_t stride, uin
     a.peer = d_peer;
     a.descs = d_descs;
     return hip_rc(launch_route_resolve(outgoing, a, s));
+}
+
+// qgcm_frames_resolve: resolve() for a batch that is still packed; the table pointer is taken the same way.
+int frames_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_frame *d_frames, uint32_t n,
+                   uint8_t *d_arena, uint64_t stride, uint32_t *d_lens, uint32_t *d_peer, qgcm_desc *d_descs, hipStream_t s) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || stride < 8 || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
+    if (n && (!d_packed || !d_frames || !d_arena || !d_lens || !d_peer || !d_descs)) return QGCM_E_ARG;
+    if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_frames & 7) || ((uintptr_t)d_arena & 3) || ((uintptr_t)d_lens & 3) ||
+        ((uintptr_t)d_peer & 3) || ((uintptr_t)d_descs & 15))
+        return QGCM_E_ARG;
+    std::lock_guard<std::mutex> g(r->mu);
+    if (!r->set) return QGCM_E_ARG;
+    if (n == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    FramesArgs a{};
+    a.packed = d_packed;
+    a.packed_len = packed_len;
+    a.frames = d_frames;
+    a.n = n;
+    a.arena = d_arena;
+    a.stride = stride;
+    a.lens = d_lens;
+    a.peer = d_peer;
+    a.descs = d_descs;
+    a.table = r->d_table;
+    a.cap_mask = r->cap_mask;
+    a.net = r->net.net;
+    a.mask = r->net.mask;
+    a.gateway = r->net.gateway;
+    a.own_ip = r->net.own_ip;
+    return hip_rc(launch_frames_resolve(a, s));
 }
 
 template <typename T>
@@ -610,6 +651,93 @@ int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_l
     return dropped;
 }
 
+// Outgoing.pipeline for a batch that was read packed (qgcm_tun_read_packed): run_route_host's packed outgoing
+// chain (`tk`) with the copy-in replaced.  Frame i is slot i, so the chunks are run_route_host's; per chunk the
+// packed bytes its frames span (the table ascends: from the first frame's off to the last frame's end) and their
+// table entries (rebased to the span) go up, frames_resolve_kernel puts them into the device arena and resolves
+// them, and chain, plan, train pack, accounting and the copy back follow as in run_route_host.
+int run_route_frames_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_frame *frames, uint64_t stride,
+                          uint32_t n, uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins, uint32_t *h_peer,
+                          uint8_t *h_status, TrainOut &tk) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || stride < 8 || n > QGCM_MAX_BATCH || !h_nonces || (plugins & ~kAllPlugins)) return QGCM_E_ARG;
+    if (n && (!h_packed || !frames || !h_lens || !h_peer)) return QGCM_E_ARG;
+    if (!frames_table_ascends(frames, n, packed_len)) return QGCM_E_ARG;
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+    }
+    if (n == 0) return 0;
+    const bool gen = h_nonces == QGCM_NONCES_GENERATE;
+    std::lock_guard<std::mutex> pg(r->pipe_mu);
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
+        r->stream = nullptr;
+        return QGCM_E_HIP;
+    }
+    hipStream_t s = r->stream;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(kRouteChunk, n),
+                                                        std::max<uint64_t>(1, kRouteChunkBytes / stride));
+    // the longest span of a chunk's frames
+    uint64_t max_span = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+        const qgcm_frame &last = frames[c0 + std::min(chunk, n - c0) - 1];
+        max_span = std::max<uint64_t>(max_span, (uint64_t)last.off + last.len - frames[c0].off);
+    }
+    // side buffer of a chunk as in run_route_host; the table (16-B aligned) and the packed bytes (16-B aligned,
+    // rounded up to 16 B) in a staging area of their own
+    const size_t o_desc = 0, o_lens = o_desc + 16ull * chunk, o_peer = o_lens + 4ull * chunk, o_non = o_peer + 4ull * chunk,
+                 o_stat = o_non + 12ull * chunk, o_bytes = (o_stat + chunk + 15) & ~(size_t)15,
+                 o_work = o_bytes + 4 * (size_t)chain_work_lanes(chunk), side = o_work + QGCM_CHAIN_WORK(chunk);
+    const size_t o_packed = (8ull * chunk + 15) & ~(size_t)15, staging = o_packed + (size_t)((max_span + 15) & ~(uint64_t)15);
+    if (!grow(r->d_arena, r->arena_cap, (size_t)chunk * stride) || !grow(r->d_side, r->side_cap, side) ||
+        !grow(r->d_frames, r->frames_cap, std::max<size_t>(staging, 16)) || !train_grow(r, tk, chunk, stride))
+        return QGCM_E_NOMEM;
+    r->h_stat.resize(chunk);
+    r->h_frames.resize(chunk);
+    qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
+    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
+    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
+    uint8_t *d_non = r->d_side + o_non, *d_stat = r->d_side + o_stat;
+    uint32_t *d_bytes = reinterpret_cast<uint32_t *>(r->d_side + o_bytes);
+    qgcm_frame *d_frames = reinterpret_cast<qgcm_frame *>(r->d_frames);
+    uint8_t *d_packed = r->d_frames + o_packed;
+    int dropped = 0;
+    for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+        const uint32_t cn = std::min(chunk, n - c0);
+        const uint64_t lo = frames[c0].off, hi = (uint64_t)frames[c0 + cn - 1].off + frames[c0 + cn - 1].len;
+        for (uint32_t j = 0; j < cn; ++j) r->h_frames[j] = qgcm_frame{(uint32_t)(frames[c0 + j].off - lo), frames[c0 + j].len};
+        int rc = QGCM_OK;
+        if ((hi > lo && hipMemcpyAsync(d_packed, h_packed + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, s) != hipSuccess) ||
+            hipMemcpyAsync(d_frames, r->h_frames.data(), 8ull * cn, hipMemcpyHostToDevice, s) != hipSuccess ||
+            (!gen && hipMemcpyAsync(d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, s) != hipSuccess))
+            rc = QGCM_E_HIP;
+        if (rc == QGCM_OK)
+            rc = frames_resolve(ctx, d_packed, hi - lo, d_frames, cn, r->d_arena, stride, d_lens, d_peer, d_descs, s);
+        if (rc == QGCM_OK)
+            rc = run_chain(ctx, true, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, gen ? QGCM_NONCES_GENERATE : d_non,
+                           d_stat, d_bytes, r->d_side + o_work, s);
+        if (rc == QGCM_OK) rc = train_chunk(tk, ctx_max_keys(ctx), r->d_arena, stride, c0, cn, d_lens, d_peer, s);
+        if (rc == QGCM_OK) rc = account(ctx, QGCM_TX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
+        if (rc == QGCM_OK &&
+            (!train_copy_back(tk, s) || hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess))
+            rc = QGCM_E_HIP;
+        // every way out waits for the stream: the next call reuses the staging, and the caller its arrays
+        if (hipStreamSynchronize(s) != hipSuccess && rc == QGCM_OK) rc = QGCM_E_HIP;
+        if (rc != QGCM_OK) return rc;
+        train_rebase(tk, c0, cn);
+        for (uint32_t i = 0; i < cn; ++i) {
+            const bool ok = r->h_stat[i] == 1;
+            if (h_status) h_status[c0 + i] = ok ? 1 : 0;
+            dropped += !ok;
+        }
+    }
+    return dropped;
+}
+
 }  // namespace
 
 extern "C" {
@@ -897,6 +1025,27 @@ int qgcm_route_chain_seal_packed_host(qgcm_ctx *ctx, const uint8_t *h_arena, uin
     // the arena is only read: with `tk` the copy back never names it
     return run_route_host(ctx, true, const_cast<uint8_t *>(h_arena), stride, n, h_lens, h_nonces, h_peer, h_status, true,
                           plugins, nullptr, &tk);
+}
+
+int qgcm_frames_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_frame *d_frames, uint32_t n,
+                        uint8_t *d_arena, uint64_t stride, uint32_t *d_lens, uint32_t *d_peer, qgcm_desc *d_descs, void *stream) {
+    return frames_resolve(ctx, d_packed, packed_len, d_frames, n, d_arena, stride, d_lens, d_peer, d_descs, (hipStream_t)stream);
+}
+
+int qgcm_frames_unpack_cpu(const uint8_t *packed, uint64_t packed_len, const qgcm_frame *frames, uint32_t n, uint8_t *arena,
+                           uint64_t stride, uint32_t *lens) {
+    return frames_unpack_checked(packed, packed_len, frames, n, arena, stride, lens);
+}
+
+int qgcm_route_chain_seal_frames_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_frame *frames,
+                                      uint64_t stride, uint32_t n, uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins,
+                                      const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status, uint8_t *h_out,
+                                      uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order, uint64_t out[4]) {
+    if (!out || (n && (!h_out || !h_ptrains))) return QGCM_E_ARG;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    TrainOut tk{h_out, std::min<uint64_t>(out_cap, kTrainMaxCap), h_ptrains, h_order, out};
+    if (!plan_limits_resolve(limits, &tk.lim)) return QGCM_E_ARG;
+    return run_route_frames_host(ctx, h_packed, packed_len, frames, stride, n, h_lens, h_nonces, plugins, h_peer, h_status, tk);
 }
 
 int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]) {

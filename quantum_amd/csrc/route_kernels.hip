@@ -17,6 +17,7 @@
 // workgroup, not per packet.  The byte counts come from the descriptors (qgcm_route_account) or from an array
 // (qgcm_route_account_bytes): one kernel, a template parameter.
 #include "gcm_internal.h"
+#include "route_core.h"  // route_lookup: shared with frames_kernels.hip
 
 namespace qgcm {
 namespace {
@@ -25,18 +26,6 @@ constexpr uint32_t kRouteThreads = 256;
 constexpr uint32_t kAcctSlots = 256;    // LDS link entries per workgroup
 constexpr uint32_t kAcctRounds = 2;     // in-wave combining rounds
 constexpr uint32_t kAcctWgsPerCu = 8;
-
-__device__ __forceinline__ uint32_t route_lookup(const uint2 *table, uint32_t cap_mask, uint32_t ip) {
-    uint32_t h = route_hash(ip) & cap_mask;
-    // at most `capacity` probes: a table without an empty entry (never built by qgcm_routes_set) ends too
-    for (uint32_t probes = 0; probes <= cap_mask; ++probes) {
-        const uint2 e = table[h];  // {ip, peer} in one 8-byte load
-        if (e.y == QGCM_NO_PEER) return QGCM_NO_PEER;
-        if (e.x == ip) return e.y;
-        h = (h + 1) & cap_mask;
-    }
-    return QGCM_NO_PEER;
-}
 
 template <bool kOutgoing>
 __global__ void __launch_bounds__(kRouteThreads) route_resolve_kernel(RouteArgs a) {

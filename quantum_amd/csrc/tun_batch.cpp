@@ -34,6 +34,7 @@
 #include <atomic>
 
 #include "../../include/qgcm.h"
+#include "frames_core.h"
 #include "pack_core.h"
 
 namespace {
@@ -332,6 +333,73 @@ int qgcm_tun_read_slots(int fd, uint8_t *arena, uint64_t stride, uint32_t max_n,
         lens[got++] = (uint32_t)n;
     }
     return (int)got;
+}
+
+// qgcm_tun_read_slots for a packed area (include/qgcm.h "outgoing frames packed on routed batches"): the same
+// wait for the first packet and the same drain, each packet read straight to the fill position rounded up to
+// 16, one qgcm_frame a packet.  A read is made only with kFrameRoom bytes of room, more than any TUN packet, so
+// no frame is cut and no length has to be known first.  preadv2(RWF_NOWAIT) per packet also with
+// QGCM_TUN_URING=1: a ring submission names its destinations before any length is known, so it cannot lay
+// frames back to back; poll + read where RWF_NOWAIT is refused or with QGCM_TUN_URING=-1.
+int qgcm_tun_read_packed(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_frame *frames, uint32_t max_n, int timeout_ms,
+                         uint64_t out[2]) {
+    using qgcm::kFrameRoom;
+    if (out) out[0] = out[1] = 0;
+    if (fd < 0 || !packed || !frames || packed_cap < kFrameRoom) return -1;
+    if (max_n == 0) return 0;
+    pollfd p{fd, POLLIN, 0};
+    int pr;
+    do {
+        pr = poll(&p, 1, timeout_ms);
+    } while (pr < 0 && errno == EINTR);
+    if (pr < 0) return -1;
+    if (pr == 0) return 0;
+    // `off` is 32 bits: the area counts up to 4 GiB
+    const uint64_t cap = packed_cap < (1ull << 32) ? packed_cap : (1ull << 32);
+    uint32_t got = 0;
+    uint64_t at = 0, end = 0;  // where the next frame goes; the end of the last one
+    auto landed = [&](ssize_t n) {
+        frames[got++] = qgcm_frame{(uint32_t)at, (uint32_t)n};
+        end = at + (uint64_t)n;
+        at = (end + 15) & ~(uint64_t)15;
+    };
+    auto done = [&](int rc) {
+        if (out && rc >= 0) out[0] = got, out[1] = end;
+        return rc;
+    };
+    static std::atomic<int> nowait_ok{1};
+    if (read_mode() == 2) nowait_ok.store(0, std::memory_order_relaxed);
+    while (got < max_n && at + kFrameRoom <= cap && nowait_ok.load(std::memory_order_relaxed)) {
+        iovec v{packed + at, (size_t)kFrameRoom};
+        const ssize_t n = preadv2(fd, &v, 1, -1, RWF_NOWAIT);
+        if (n < 0) {
+            if (errno == EINTR) continue;
+            if (errno == EAGAIN || errno == EWOULDBLOCK) return done((int)got);
+            if (errno == EOPNOTSUPP || errno == EINVAL || errno == ENOSYS) {
+                nowait_ok.store(0, std::memory_order_relaxed);
+                break;
+            }
+            return done(got ? (int)got : -1);
+        }
+        landed(n);
+    }
+    while (got < max_n && at + kFrameRoom <= cap) {
+        if (got) {  // drain without blocking: only what is already queued joins this batch
+            p.revents = 0;
+            do {
+                pr = poll(&p, 1, 0);
+            } while (pr < 0 && errno == EINTR);
+            if (pr <= 0) break;
+        }
+        const ssize_t n = read(fd, packed + at, (size_t)kFrameRoom);
+        if (n < 0) {
+            if (errno == EINTR) continue;
+            if (errno == EAGAIN || errno == EWOULDBLOCK) break;
+            return done(got ? (int)got : -1);
+        }
+        landed(n);
+    }
+    return done((int)got);
 }
 
 // device/tun.go:60-63, batched: writes Raw[4 : 4 + lens[i]] of slots 0..n-1 (payload.Packet after

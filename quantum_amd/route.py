@@ -21,6 +21,8 @@ socket/udp.go:35-41        Read, as coalesced UDP_GRO buffers unpacked into slot
 device/tun.go:60-63        Write, from delivered packets packed back to back on the GPU -> deliver_pack,
                            deliver_pack_cpu, tun_write_packed, route_chain_open_packed_host,
                            route_chain_open_gro_packed_host
+device/tun.go:51-57        Read, packed back to back and put into slots and resolved on the GPU -> tun_read_packed,
+                           frames_resolve, frames_unpack_cpu, route_chain_seal_frames_host
 """
 from __future__ import annotations
 
@@ -547,4 +549,53 @@ def route_chain_seal_packed_host(ctx, arena_ptr: int, stride: int, n: int, lens,
                                                       order.ctypes.data, out.ctypes.data)
     if rc < 0 and rc != _lib.QGCM_E_NOMEM:
         _lib.check(rc, "qgcm_route_chain_seal_packed_host")
+    return rc, ptrains[:int(out[1])], order[:int(out[3])], out
+
+
+def tun_read_packed(fd: int, packed, frames, max_n: int, timeout_ms: int, out=None) -> int:
+    """qgcm_tun_read_packed into `packed` (a contiguous numpy uint8 array of at least 65536 bytes, the packed
+    area) and `frames` (a numpy uint32 array of shape (max_n or more, 2): off, len per packet); `out` a numpy
+    uint64 array of 2 ({frames, bytes used}) or None.  Returns the number of packets, 0 on timeout, or -1."""
+    return _lib.lib().qgcm_tun_read_packed(fd, packed.ctypes.data, packed.size, frames.ctypes.data,
+                                           min(max_n, len(frames)), timeout_ms, None if out is None else out.ctypes.data)
+
+
+def frames_resolve(ctx, packed, packed_len: int, frames, n: int, arena, stride: int, lens, peer, descs, stream=None) -> None:
+    """qgcm_frames_resolve on device tensors: `packed` uint8 (16-B aligned, its size rounded up to 16 B), `frames`
+    int32 (2 n: off, len per frame), `lens` / `peer` int32 (n), `descs` uint8 (16 n bytes); chain_outgoing follows
+    on the same stream."""
+    _lib.check(_lib.lib().qgcm_frames_resolve(ctx.handle, _ptr(packed), packed_len, _ptr(frames), n, _ptr(arena), stride,
+                                              _ptr(lens), _ptr(peer), _ptr(descs), _stream_handle(stream)),
+               "qgcm_frames_resolve")
+
+
+def frames_unpack_cpu(packed, packed_len: int, frames, arena, stride: int, lens) -> None:
+    """qgcm_frames_unpack_cpu over numpy arrays: `packed` / `arena` uint8, `frames` uint32 (n, 2), `lens` uint32
+    (n).  Raises for a table with a frame that is not valid, with nothing written."""
+    _lib.check(_lib.lib().qgcm_frames_unpack_cpu(packed.ctypes.data, packed_len, frames.ctypes.data, len(frames),
+                                                 arena.ctypes.data, stride, lens.ctypes.data), "qgcm_frames_unpack_cpu")
+
+
+def route_chain_seal_frames_host(ctx, packed, packed_len: int, frames, stride: int, n: int, lens, nonces, plugins: int,
+                                 peer, status, out_buf, limits=None, ptrains=None, order=None):
+    """qgcm_route_chain_seal_frames_host: route_chain_seal_packed_host for what tun_read_packed left in `packed`
+    and `frames` (numpy uint32 (n, 2)); `lens` is output only, `nonces` a host address or batch.GENERATE (None is
+    refused).  Returns as route_chain_seal_packed_host; after QGCM_E_NOMEM repeat with frames[out[0]:]."""
+    import numpy as np
+
+    from .batch import GENERATE
+
+    if ptrains is None:
+        ptrains = np.zeros((max(1, n), 4), np.uint32)
+    if order is None:
+        order = np.zeros(max(1, n), np.uint32)
+    out = np.zeros(4, np.uint64)
+    np_ = _lib.NONCES_GENERATE if nonces is GENERATE else nonces
+    rc = _lib.lib().qgcm_route_chain_seal_frames_host(ctx.handle, packed.ctypes.data, packed_len, frames.ctypes.data,
+                                                      stride, n, lens.ctypes.data, np_, plugins, _limits_ptr(limits),
+                                                      peer.ctypes.data, None if status is None else status.ctypes.data,
+                                                      out_buf.ctypes.data, out_buf.size, ptrains.ctypes.data,
+                                                      order.ctypes.data, out.ctypes.data)
+    if rc < 0 and rc != _lib.QGCM_E_NOMEM:
+        _lib.check(rc, "qgcm_route_chain_seal_frames_host")
     return rc, ptrains[:int(out[1])], order[:int(out[3])], out
