@@ -27,7 +27,8 @@
  *                                                                qgcm_route_chain_seal_packed_host
  *   socket/udp.go:35-41 Read() for a batch                    -> qgcm_udp_recv_slots, or coalesced (UDP_GRO):
  *                                                                qgcm_udp_recv_gro + qgcm_gro_unpack /
- *                                                                qgcm_route_chain_open_gro_host
+ *                                                                qgcm_gro_resolve (unpack and resolve in one
+ *                                                                launch) / qgcm_route_chain_open_gro_host
  *   device/tun.go:60-63 Write(payload) for a batch            -> qgcm_tun_write_slots, or packed on the GPU:
  *                                                                qgcm_deliver_pack + qgcm_tun_write_packed /
  *                                                                qgcm_route_chain_open_gro_packed_host
@@ -713,6 +714,25 @@ int qgcm_udp_send_plan(int fd, const uint8_t *arena, uint64_t stride, uint32_t n
  * by a binary search over them); a table in which they do not is memory-safe, and which of its slots are
  * written is unspecified.  n == 0 or n_bufs == 0: QGCM_OK, nothing launched.  n > QGCM_MAX_BATCH, n_bufs > n,
  * a bad stride, a NULL or misaligned pointer: QGCM_E_ARG.
+ * qgcm_gro_resolve: qgcm_gro_unpack and qgcm_resolve_incoming of the same arrays in one launch: device arrays,
+ * asynchronous on stream, no context state beyond the route table (calls on several streams may run at once).
+ * It leaves in the arena, d_lens, d_peer and d_descs exactly what
+ *   qgcm_gro_unpack(ctx, d_packed, packed_len, d_bufs, n_bufs, n, d_arena, stride, d_lens, stream) and then
+ *   qgcm_resolve_incoming(ctx, d_arena, stride, n, d_lens, d_peer, d_descs, stream)
+ * leave, byte for byte.  Datagram k of a buffer that is not skipped (slot i = first + k, length L): d_lens[i] = L,
+ * bytes [0, min(L, stride)) of the slot are the datagram's and the slot's tail keeps its bytes; the packet is
+ * readable when 4 <= L <= stride, its peer then the route of key = in-net(addr) ? addr : gateway with addr the
+ * datagram's first four bytes -- read from the packed area, not from the slot -- and else QGCM_NO_PEER;
+ * d_descs[i] = {i * stride, L >= 4 ? L - 4 : 0, peer}, d_peer[i] = peer.  A slot i < n that no unskipped buffer
+ * names (a gap in `first`, a buffer past packed_len or past n) keeps d_lens[i] and its bytes, and its peer and
+ * descriptor are resolved from that length and from Raw[0:4] as they were: d_lens is input and output, as it is
+ * for the pair.  n_bufs == 0 with n > 0 is qgcm_resolve_incoming.  n == 0: QGCM_OK, nothing launched.  A table
+ * whose `first` values do not ascend is memory-safe as for qgcm_gro_unpack (every table index is checked
+ * against n_bufs, every source byte against packed_len, every slot against n); which slots are written, and
+ * with what, is then unspecified.  QGCM_E_ARG with nothing launched: a NULL ctx, n > QGCM_MAX_BATCH, n_bufs > n,
+ * a stride that is zero or not a multiple of 4, any NULL array when n > 0, d_packed, d_bufs or d_descs off a
+ * 16-B boundary, d_arena, d_lens or d_peer off a 4-B boundary, a context without qgcm_routes_set.  The read
+ * bound is qgcm_gro_unpack's: up to the 16-B boundary behind packed_len, never further.
  * qgcm_gro_unpack_cpu: the same for host arrays (no alignment asked), by the host, so that a worker can use
  * the coalesced receive with qgcm_route_open_host.  It checks the table first: each `first` is the exclusive
  * prefix sum of the counts before it and the counts total n; if not, QGCM_E_ARG and nothing is written.
@@ -722,8 +742,9 @@ int qgcm_udp_send_plan(int fd, const uint8_t *arena, uint64_t stride, uint32_t n
  * (QGCM_E_ARG, nothing launched).  The batch is cut into chunks at buffer boundaries under the packet and
  * byte limits of those calls (a buffer with more datagrams than a chunk holds is a chunk of its own); per
  * chunk only the chunk's packed bytes and table entries are copied up, unpacked into the context's device
- * arena, then resolved, opened or chained, accounted and copied back as in those calls, serialised on the
- * context's routed stream like them.  h_lens is output only.  h_peer, h_status, h_lens, the return value
+ * arena and resolved (qgcm_gro_unpack, then the resolve; the one launch of qgcm_gro_resolve when
+ * QGCM_GRO_FUSED=1 was in the environment at qgcm_create -- the outputs are the same), then opened or chained,
+ * accounted and copied back as in those calls, serialised on the context's routed stream like them.  h_lens is output only.  h_peer, h_status, h_lens, the return value
  * and the Rx counters are what the existing call gives for the arena and lengths that qgcm_gro_unpack_cpu
  * makes of the same input (a buffer past packed_len counts as datagrams of length 0); delivered packets are
  * equal over Raw[:4 + h_lens[i]], dropped ones over Raw[:datagram length].  The slot bytes behind that are
@@ -735,6 +756,9 @@ int qgcm_udp_recv_gro(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_gro_buf
                       uint32_t max_n, int timeout_ms, uint64_t out[3]);
 int qgcm_gro_unpack(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gro_buf *d_bufs,
                     uint32_t n_bufs, uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens, void *stream);
+int qgcm_gro_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gro_buf *d_bufs,
+                     uint32_t n_bufs, uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens,
+                     uint32_t *d_peer, qgcm_desc *d_descs, void *stream);
 int qgcm_gro_unpack_cpu(const uint8_t *packed, uint64_t packed_len, const qgcm_gro_buf *bufs, uint32_t n_bufs,
                         uint32_t n, uint8_t *arena, uint64_t stride, uint32_t *lens);
 int qgcm_route_open_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gro_buf *bufs,

@@ -49,6 +49,7 @@ EXPORTS = (
     "qgcm_train_pack_work", "qgcm_train_pack", "qgcm_train_pack_cpu", "qgcm_udp_send_packed",
     "qgcm_route_chain_seal_packed_host",
     "qgcm_tun_read_packed", "qgcm_frames_resolve", "qgcm_frames_unpack_cpu", "qgcm_route_chain_seal_frames_host",
+    "qgcm_gro_resolve",
 )
 
 QGCM_OK = 0
@@ -295,6 +296,8 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_frames_resolve.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp]
         L.qgcm_frames_unpack_cpu.argtypes = [vp, u64, vp, u32, vp, u64, vp]
         L.qgcm_route_chain_seal_frames_host.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp]
+    if hasattr(L, "qgcm_gro_resolve"):  # (older builds loaded by the A/B tools lack the fused receive)
+        L.qgcm_gro_resolve.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, vp, vp, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

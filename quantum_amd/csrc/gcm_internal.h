@@ -424,6 +424,25 @@ struct FramesArgs {
     uint32_t net, mask, gateway, own_ip;
 };
 hipError_t launch_frames_resolve(const FramesArgs &a, hipStream_t s);
+// Coalesced receive buffers unpacked into slots and resolved (gro_resolve_kernels.hip; include/qgcm.h "coalesced
+// receive on routed batches"): what launch_gro_unpack and then route_resolve_kernel<incoming> leave, one launch
+// on s (the 16-byte path when stride and arena allow it, else the dword path).  packed and bufs are 16-B aligned,
+// packed readable up to the 16-B boundary behind packed_len; 1 <= n_bufs <= n (the caller resolves a batch
+// without a table with launch_route_resolve); the caller has checked the arguments.
+struct GroResolveArgs {
+    const uint8_t *packed;
+    uint64_t packed_len;
+    const qgcm_gro_buf *bufs;  // 16-B aligned
+    uint32_t n_bufs, n;
+    uint8_t *arena;
+    uint64_t stride;
+    uint32_t *lens, *peer;     // lens: read for the slots no buffer names, written for the others
+    qgcm_desc *descs;          // 16-B aligned
+    const uint2 *table;
+    uint32_t cap_mask;
+    uint32_t net, mask, gateway;
+};
+hipError_t launch_gro_resolve(const GroResolveArgs &a, hipStream_t s);
 // qgcm_send_plan_host plans on the device from this many packets on (QGCM_PLAN_DEVICE_MIN at qgcm_create): the
 // measured crossover -- 181 against 186 us at 65536, 319 against 993 us at 262144
 constexpr uint32_t kPlanDeviceMin = 65536;

@@ -1,7 +1,8 @@
 // gro_core.h -- the coalesced receive of include/qgcm.h ("coalesced receive on routed batches") as plain
-// C++: the datagram count of a buffer, the skip rule, the table check of the host entry points and the host
-// unpack.  No HIP, no allocation: qgcm_gro_unpack_cpu runs it, gro_kernels.hip shares the count and the skip
-// rule with it, route.cpp checks its tables with it, and tests/cpp_gro builds it under the host sanitizers.
+// C++: the datagram count of a buffer, the skip rule, the search of a slot's buffer, the table check of the host
+// entry points and the host unpack.  No HIP, no allocation: qgcm_gro_unpack_cpu runs it, gro_kernels.hip and
+// gro_resolve_kernels.hip share the count, the skip rule and the search with it, route.cpp checks its tables
+// with it, and tests/cpp_gro and tests/cpp_gro_resolve build it under the host sanitizers.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -33,6 +34,43 @@ QGCM_GRO_HD inline uint32_t gro_seg_bytes(uint32_t len, uint32_t seg_len, uint64
 // A buffer that reaches past the packed area or past slot n is skipped whole.
 QGCM_GRO_HD inline bool gro_buf_skipped(const qgcm_gro_buf &b, uint64_t count, uint64_t packed_len, uint32_t n) {
     return (uint64_t)b.off + b.len > packed_len || (uint64_t)b.first + count > n;
+}
+
+// The buffer of slot i (i < n, n_bufs >= 1): the index of the last buffer whose first is at or below i (0 when
+// none is) in a table whose `first` values ascend; on any other table some index below n_bufs.  Every read of
+// the table lies below n_bufs.  The search of gro_unpack_kernel and gro_resolve_kernel, and tests/cpp_gro_resolve
+// runs it on the host.
+QGCM_GRO_HD inline uint32_t gro_find(const qgcm_gro_buf *bufs, uint32_t n_bufs, uint32_t n, uint64_t i) {
+    // the last buffer whose first is at or below i, kept in [lo, hi): bufs[lo].first <= i unless lo is 0,
+    // bufs[hi].first > i unless hi is n_bufs.  Buffers of equal counts would put slot i into buffer
+    // i * n_bufs / n; the bracket is grown from there in doubling steps, then halved.
+    uint32_t lo = 0, hi = n_bufs;
+    const uint32_t guess = (uint32_t)(i * n_bufs / n);
+    if (bufs[guess].first <= i) {
+        lo = guess;
+        uint32_t step = 1;
+        while (hi - lo > step && bufs[lo + step].first <= i) {
+            lo += step;
+            step <<= 1;
+        }
+        if (hi - lo > step) hi = lo + step;
+    } else {
+        hi = guess;
+        uint32_t step = 1;
+        while (step <= hi && bufs[hi - step].first > i) {
+            hi -= step;
+            step <<= 1;
+        }
+        lo = step <= hi ? hi - step : 0;
+    }
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (bufs[mid].first <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
 }
 
 // What the host entry points ask of a table: each `first` the exclusive prefix sum of the counts before it,

@@ -53,6 +53,12 @@ struct RouteState {
     size_t plan_cap = 0;
     uint32_t plan_device_min = kPlanDeviceMin;
 
+    // the coalesced-receive pipelines unpack and resolve a chunk with gro_unpack_kernel and the resolve kernel;
+    // QGCM_GRO_FUSED=1 when the context is created selects the one launch of qgcm_gro_resolve instead (same
+    // outputs).  The pair is the default because the pipeline measured 1-2 % slower with the one launch: a
+    // chunk of 65536 slots gives it 1024 waves where the unpack has 16384
+    bool gro_fused = false;
+
     // the coalesced-receive pipelines: a chunk's table and packed bytes on the device, the rebased table on
     // the host (under pipe_mu, on `stream`)
     uint8_t *d_gro = nullptr;
@@ -80,6 +86,8 @@ RouteState *route_state_create() {
     RouteState *r = new RouteState();
     if (const char *v = getenv("QGCM_PLAN_DEVICE_MIN"))
         if (*v) r->plan_device_min = (uint32_t)std::min<unsigned long long>(strtoull(v, nullptr, 0), 0xffffffffull);
+    if (const char *v = getenv("QGCM_GRO_FUSED"))
+        if (*v) r->gro_fused = strtoull(v, nullptr, 0) != 0;
     return r;
 }
 
@@ -166,6 +174,57 @@ int frames_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, 
     a.gateway = r->net.gateway;
     a.own_ip = r->net.own_ip;
     return hip_rc(launch_frames_resolve(a, s));
+}
+
+// qgcm_gro_resolve: resolve(ctx, false, ...) for a batch that is still in its coalesced buffers; the table pointer
+// is taken the same way.  Without a table there is nothing to unpack: the existing resolve kernel.
+int gro_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gro_buf *d_bufs, uint32_t n_bufs,
+                uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens, uint32_t *d_peer, qgcm_desc *d_descs,
+                hipStream_t s) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || stride == 0 || n > QGCM_MAX_BATCH || n_bufs > n) return QGCM_E_ARG;
+    if (n && (!d_packed || !d_bufs || !d_arena || !d_lens || !d_peer || !d_descs)) return QGCM_E_ARG;
+    if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_bufs & 15) || ((uintptr_t)d_arena & 3) || ((uintptr_t)d_lens & 3) ||
+        ((uintptr_t)d_peer & 3) || ((uintptr_t)d_descs & 15))
+        return QGCM_E_ARG;
+    std::lock_guard<std::mutex> g(r->mu);
+    if (!r->set) return QGCM_E_ARG;
+    if (n == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    if (n_bufs == 0) {
+        RouteArgs ra{};
+        ra.table = r->d_table;
+        ra.cap_mask = r->cap_mask;
+        ra.net = r->net.net;
+        ra.mask = r->net.mask;
+        ra.gateway = r->net.gateway;
+        ra.own_ip = r->net.own_ip;
+        ra.arena = d_arena;
+        ra.stride = stride;
+        ra.n = n;
+        ra.lens = d_lens;
+        ra.peer = d_peer;
+        ra.descs = d_descs;
+        return hip_rc(launch_route_resolve(false, ra, s));
+    }
+    GroResolveArgs a{};
+    a.packed = d_packed;
+    a.packed_len = packed_len;
+    a.bufs = d_bufs;
+    a.n_bufs = n_bufs;
+    a.n = n;
+    a.arena = d_arena;
+    a.stride = stride;
+    a.lens = d_lens;
+    a.peer = d_peer;
+    a.descs = d_descs;
+    a.table = r->d_table;
+    a.cap_mask = r->cap_mask;
+    a.net = r->net.net;
+    a.mask = r->net.mask;
+    a.gateway = r->net.gateway;
+    return hip_rc(launch_gro_resolve(a, s));
 }
 
 template <typename T>
@@ -536,8 +595,8 @@ int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, 
 // Incoming.pipeline for a batch that arrived as coalesced buffers (qgcm_udp_recv_gro): run_route_host's open
 // side with the copy-in replaced.  Chunks end at buffer boundaries; per chunk the packed bytes its buffers
 // span and their table entries (rebased to the span and to the chunk's first slot) go up, gro_unpack_kernel
-// scatters them into the device arena, and resolve, open or chain, accounting and the copy back follow as in
-// run_route_host.  The lengths start as zeros on the device, so the slots of a buffer the kernel skips (one
+// scatters them into the device arena and the resolve kernel resolves them (QGCM_GRO_FUSED=1: gro_resolve_kernel
+// does both), and open or chain, accounting and the copy back follow as in run_route_host.  The lengths start as zeros on the device, so the slots of a buffer the kernel skips (one
 // past packed_len) are datagrams of length 0.
 int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gro_buf *bufs,
                        uint32_t n_bufs, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens, uint32_t *h_peer,
@@ -619,8 +678,13 @@ int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_l
             (c.hi > c.lo && hipMemcpyAsync(d_packed, h_packed + c.lo, (size_t)(c.hi - c.lo), hipMemcpyHostToDevice, s) != hipSuccess) ||
             hipMemcpyAsync(d_bufs, r->h_gro.data(), 16ull * nb, hipMemcpyHostToDevice, s) != hipSuccess)
             return QGCM_E_HIP;
-        int rc = hip_rc(launch_gro_unpack(d_packed, c.hi - c.lo, d_bufs, nb, cn, r->d_arena, stride, d_lens, s));
-        if (rc == QGCM_OK) rc = resolve(ctx, false, r->d_arena, stride, cn, d_lens, d_peer, d_descs, s);
+        int rc;
+        if (r->gro_fused) {
+            rc = gro_resolve(ctx, d_packed, c.hi - c.lo, d_bufs, nb, cn, r->d_arena, stride, d_lens, d_peer, d_descs, s);
+        } else {
+            rc = hip_rc(launch_gro_unpack(d_packed, c.hi - c.lo, d_bufs, nb, cn, r->d_arena, stride, d_lens, s));
+            if (rc == QGCM_OK) rc = resolve(ctx, false, r->d_arena, stride, cn, d_lens, d_peer, d_descs, s);
+        }
         if (rc == QGCM_OK && chain) {
             rc = run_chain(ctx, false, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, nullptr, d_stat, d_bytes,
                            r->d_side + o_work, s);
@@ -936,6 +1000,13 @@ int qgcm_gro_unpack(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len,
     if (n == 0 || n_bufs == 0) return QGCM_OK;
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
     return hip_rc(launch_gro_unpack(d_packed, packed_len, d_bufs, n_bufs, n, d_arena, stride, d_lens, (hipStream_t)stream));
+}
+
+int qgcm_gro_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gro_buf *d_bufs,
+                     uint32_t n_bufs, uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens,
+                     uint32_t *d_peer, qgcm_desc *d_descs, void *stream) {
+    return gro_resolve(ctx, d_packed, packed_len, d_bufs, n_bufs, n, d_arena, stride, d_lens, d_peer, d_descs,
+                       (hipStream_t)stream);
 }
 
 int qgcm_gro_unpack_cpu(const uint8_t *packed, uint64_t packed_len, const qgcm_gro_buf *bufs, uint32_t n_bufs,

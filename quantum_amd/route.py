@@ -17,7 +17,8 @@ plugin/compression.go:31-33, plugin/encryption.go:17-19  the per-peer gate -> pe
 socket/udp.go:43-47        Write, grouped per peer into UDP_SEGMENT trains -> send_plan, send_plan_host,
                            send_plan_cpu, udp_send_plan
 socket/udp.go:35-41        Read, as coalesced UDP_GRO buffers unpacked into slots -> udp_gro, udp_recv_gro,
-                           gro_unpack, gro_unpack_cpu, route_open_gro_host, route_chain_open_gro_host
+                           gro_unpack, gro_unpack_cpu, route_open_gro_host, route_chain_open_gro_host;
+                           unpacked and resolved in one launch -> gro_resolve
 device/tun.go:60-63        Write, from delivered packets packed back to back on the GPU -> deliver_pack,
                            deliver_pack_cpu, tun_write_packed, route_chain_open_packed_host,
                            route_chain_open_gro_packed_host
@@ -367,6 +368,16 @@ def gro_unpack(ctx, packed, packed_len: int, bufs, n_bufs: int, n: int, arena, s
     int32 (4 n_bufs), `lens` int32 (n); resolve_incoming follows on the same stream."""
     _lib.check(_lib.lib().qgcm_gro_unpack(ctx.handle, _ptr(packed), packed_len, _ptr(bufs), n_bufs, n, _ptr(arena),
                                           stride, _ptr(lens), _stream_handle(stream)), "qgcm_gro_unpack")
+
+
+def gro_resolve(ctx, packed, packed_len: int, bufs, n_bufs: int, n: int, arena, stride: int, lens, peer, descs,
+                stream=None) -> None:
+    """qgcm_gro_resolve on device tensors: gro_unpack and resolve_incoming of the same arrays in one launch.
+    `packed` uint8 (16-B aligned, its size rounded up to 16 B), `bufs` int32 (4 n_bufs), `lens` / `peer` int32 (n;
+    `lens` is read for the slots no buffer names), `descs` 16 n bytes."""
+    _lib.check(_lib.lib().qgcm_gro_resolve(ctx.handle, _ptr(packed), packed_len, _ptr(bufs), n_bufs, n, _ptr(arena),
+                                           stride, _ptr(lens), _ptr(peer), _ptr(descs), _stream_handle(stream)),
+               "qgcm_gro_resolve")
 
 
 def gro_unpack_cpu(packed, packed_len: int, bufs, n: int, arena, stride: int, lens) -> None:
