@@ -32,6 +32,11 @@
  *   device/tun.go:60-63 Write(payload) for a batch            -> qgcm_tun_write_slots, or packed on the GPU:
  *                                                                qgcm_deliver_pack + qgcm_tun_write_packed /
  *                                                                qgcm_route_chain_open_gro_packed_host
+ *   device/tun.go:51-57 Read() for a batch                    -> qgcm_tun_read_slots, or packed: qgcm_tun_read_packed +
+ *                                                                qgcm_frames_resolve, or as TSO / USO super-frames
+ *                                                                cut on the GPU: qgcm_tun_open_offload +
+ *                                                                qgcm_tun_read_gso + qgcm_gso_resolve /
+ *                                                                qgcm_route_chain_seal_gso_host
  *
  * Error convention follows the reference's own cgo layer (crypto/dtls.go:37-40, dtls.h:43-48):
  * constructors return NULL and fill a caller-supplied error buffer; everything else returns
@@ -977,6 +982,114 @@ int qgcm_route_chain_seal_frames_host(qgcm_ctx *ctx, const uint8_t *h_packed, ui
                                       const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
                                       uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains,
                                       uint32_t *h_order, uint64_t out[4]);
+
+/* ---- TUN super-frames segmented on routed batches: TSO / USO for the outgoing path ---- */
+/* A TUN queue opened with IFF_VNET_HDR and TUNSETOFFLOAD hands over one TCP (or UDP_L4) super-frame of up to 64 KiB
+ * with a 10-byte virtio_net_hdr in front, and leaves the segmentation and the L4 checksum to the reader.  Here
+ * the read lays the super-frames back to back, a table names them, and one launch on the device cuts them into
+ * the per-packet slots, lengths, peers and descriptors the chain, the plan and the train pack take: the frame
+ * crosses PCIe once, its headers not repeated.
+ *
+ * Table: entry e is the IP packet packed[off, off + len) (behind its vnet header) and names the slots
+ * [first, first + count).  One rule, from the entry alone (never from packet bytes), says whether it is valid:
+ *   every kind:  off % 16 == 0, off + len <= packed_len (64 bits), first + count <= n, kind <= 3;
+ *   PLAIN, CSUM: count == 1;
+ *   CSUM:        l4_off and csum_off even, l4_off + csum_off + 2 <= len;
+ *   TCP4, UDP4:  l4_off in [20, 60] and a multiple of 4; UDP4: hdr_len == l4_off + 8; TCP4: hdr_len - l4_off in
+ *                [20, 60] and a multiple of 4; hdr_len < len; gso_size >= 1;
+ *                count == ceil((len - hdr_len) / gso_size) and count <= QGCM_GSO_SEGS.
+ * Any other entry is void (`reserved` is not looked at).  A void entry with count >= 1 and first < n gives slot
+ * `first` the void-frame result of qgcm_frames_resolve -- d_lens = 0, QGCM_NO_PEER, descriptor {first * stride, 0,
+ * QGCM_NO_PEER}, the slot untouched -- and writes nothing for the further slots it names.
+ *
+ * Segment k of a valid TCP4 / UDP4 entry goes to slot first + k: the packet at Raw[4:] of length L_k = hdr_len +
+ * P_k, P_k = min(gso_size, len - hdr_len - k * gso_size).  Its header is the frame's first hdr_len bytes, its
+ * payload packed[off + hdr_len + k * gso_size ..).  IPv4: total length L_k (mod 2^16), identification id0 + k mod
+ * 2^16, header checksum recomputed over l4_off bytes.  TCP4: sequence number seq0 + k * gso_size mod 2^32, FIN and
+ * PSH cleared on every segment but the last, checksum from scratch over pseudo-header (protocol 6), header and
+ * payload, an odd payload padded with a zero byte; what the frame had in the field is ignored.  UDP4: UDP length
+ * 8 + P_k (mod 2^16), checksum from scratch (protocol 17), a result of 0 stored as 0xffff.  CSUM: the packet is
+ * copied and the 16-bit field at l4_off + csum_off becomes ~fold(sum of bytes [l4_off, len)), the partial value
+ * already in the field included (virtio's NEEDS_CSUM), 0 stored as 0xffff.  PLAIN: what qgcm_frames_resolve does
+ * for a frame.  For every slot written, as qgcm_frames_resolve documents: d_lens[i] is the true length, also when
+ * clamped; only Raw[4 : 4 + min(L, stride - 4)) is written (checksums are those of the whole packet); the
+ * destination is Packet[16:20], L < 20 or 4 + L + 28 > stride is a miss; own_ip into Raw[0:4] on a hit only; slot
+ * tails, Raw[0:4] of misses and slots no entry names keep their bytes, and a slot i < n no entry names keeps its
+ * d_lens, d_peer and d_descs too.
+ *
+ * `first` ascends: the host calls (qgcm_gso_unpack_cpu, qgcm_route_chain_seal_gso_host) check that every entry is
+ * valid, that each `first` is the sum of the counts before it and that the counts total n; else QGCM_E_ARG with
+ * nothing written.  qgcm_gso_resolve is memory-safe on any table: it reads the table below n_frames only, nothing
+ * behind the 16-byte boundary after packed_len and nothing of the packed area outside [off, off + len) of a valid
+ * entry rounded out to 16-byte boundaries, and it writes nothing outside the arena's n * stride bytes and entries
+ * below n of d_lens, d_peer, d_descs; a slot is written from the last entry whose `first` is at or below it, so
+ * on a table whose `first` does not ascend which slots are written is unspecified.
+ *
+ * qgcm_gso_resolve: device arrays, asynchronous on stream, one launch; the route table is taken as
+ * qgcm_frames_resolve takes it.  d_packed, d_frames and d_descs 16-B aligned, the d_packed allocation rounded up
+ * to 16 B; d_lens, d_peer and d_arena 4-B aligned; stride a multiple of 4, at least 8 (a multiple of 16 under a
+ * 16-B-aligned arena takes the 16-byte path, anything else the dword path).  n == 0 or n_frames == 0: QGCM_OK,
+ * nothing launched.  n > QGCM_MAX_BATCH, n_frames > n, a bad stride, a NULL or misaligned pointer, or a call before
+ * qgcm_routes_set: QGCM_E_ARG, nothing launched.
+ *
+ * qgcm_gso_unpack_cpu: the segmentation for host arrays (no alignment asked): lens[i] and Raw[4 : 4 + min(L,
+ * stride - 4)) of every slot, nothing else; the yardstick, and the path of a worker without a device.
+ *
+ * qgcm_tun_open_offload: qgcm_tun_open plus IFF_VNET_HDR, TUNSETVNETHDRSZ = 10 and TUNSETOFFLOAD.  `offloads`:
+ * QGCM_TUN_TSO4 asks for TUN_F_CSUM | TUN_F_TSO4, QGCM_TUN_USO adds TUN_F_CSUM | TUN_F_USO4 | TUN_F_USO6 (the
+ * kernel takes the two only as a pair); TUN_F_TSO6 and TUN_F_TSO_ECN are never set; any other bit: -EINVAL.
+ * Returns 0 or -errno (every queue opened so far closed).
+ *
+ * qgcm_tun_read_gso: qgcm_tun_read_packed for such a queue.  Each read lands so that the IP packet starts on a
+ * 16-byte boundary with the vnet header in the 10 bytes before it (the first packet at packed + 16).  It reads
+ * only with 65536 + 16 bytes of room, only with at least QGCM_GSO_SEGS slots of max_n left, and at most
+ * max_frames times, and fills one table entry a read from the vnet header: no GSO type -> PLAIN, or CSUM with
+ * NEEDS_CSUM (csum_start, csum_offset); TCPV4 -> TCP4 and UDP_L4 over IPv4 -> UDP4 with l4_off = csum_start,
+ * gso_size from the header, and the TCP header length from the packet's data-offset nibble (the vnet hdr_len is
+ * the linear part of the kernel's buffer and is not used).  A frame it does not split -- TCPV6, UDP_L4 over
+ * IPv6, UFO, the ECN bit, a read shorter than the vnet header, anything the validity rule refuses -- is written
+ * as the PLAIN entry of length 0 at its offset, which gives its one slot the void-frame result, and is counted
+ * in out[2].  Returns the number of slots named, 0 on timeout, -1 on an error (also a NULL array, packed_cap
+ * below 65536 + 16 or max_n below QGCM_GSO_SEGS); out (may be NULL) = {entries, bytes used = the end of the last
+ * frame, frames not split}.
+ *
+ * qgcm_route_chain_seal_gso_host: qgcm_route_chain_seal_frames_host with qgcm_gso_resolve in place of
+ * qgcm_frames_resolve.  The table is checked first (above).  Chunks hold whole entries, as many as fit that
+ * call's limits (65536 packets, 256 MiB of slots; a lone entry of more is a chunk of its own); per chunk only
+ * the packed bytes its entries span and the entries, rebased to the span and to the chunk's first slot, go up;
+ * everything after the first launch is that call's.  h_nonces n * 12 bytes or QGCM_NONCES_GENERATE.  The outputs
+ * are what qgcm_route_chain_seal_frames_host gives, chunked at the same slots, for the packets
+ * qgcm_gso_unpack_cpu makes.  After QGCM_E_NOMEM (out written) the call is repeated with the entries from the one
+ * whose `first` is out[0] on, their `first` reduced by out[0]. */
+#define QGCM_GSO_PLAIN 0u  /* copy only */
+#define QGCM_GSO_CSUM  1u  /* copy, complete a partial checksum */
+#define QGCM_GSO_TCP4  2u  /* split an IPv4 TCP super-frame */
+#define QGCM_GSO_UDP4  3u  /* split an IPv4 UDP (UDP_L4) super-frame */
+#define QGCM_GSO_SEGS  2048u
+#define QGCM_TUN_TSO4 1u
+#define QGCM_TUN_USO  2u
+typedef struct qgcm_gso_frame {
+    uint32_t off, len;            /* the IP packet in the packed area (behind the vnet header); off % 16 == 0 */
+    uint32_t first, count;        /* its first slot, its number of slots */
+    uint16_t gso_size, hdr_len;   /* payload bytes a segment; IP + L4 header bytes (TCP4/UDP4) */
+    uint16_t l4_off, csum_off;    /* csum_start (= IPv4 header length for TCP4/UDP4); csum_offset (CSUM only) */
+    uint32_t kind, reserved;      /* reserved = 0 */
+} qgcm_gso_frame;                 /* 32 bytes, 16-B aligned */
+int qgcm_tun_open_offload(const char *name, int queues, int *fds, char *ifname_out, size_t ifname_len,
+                          uint32_t offloads);
+int qgcm_tun_read_gso(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_gso_frame *frames, uint32_t max_frames,
+                      uint32_t max_n, int timeout_ms, uint64_t out[3]);
+int qgcm_gso_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gso_frame *d_frames,
+                     uint32_t n_frames, uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens,
+                     uint32_t *d_peer, qgcm_desc *d_descs, void *stream);
+int qgcm_gso_unpack_cpu(const uint8_t *packed, uint64_t packed_len, const qgcm_gso_frame *frames, uint32_t n_frames,
+                        uint32_t n, uint8_t *arena, uint64_t stride, uint32_t *lens);
+int qgcm_route_chain_seal_gso_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
+                                   const qgcm_gso_frame *frames, uint32_t n_frames, uint64_t stride, uint32_t n,
+                                   uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins,
+                                   const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
+                                   uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order,
+                                   uint64_t out[4]);
 
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19

@@ -50,6 +50,8 @@ EXPORTS = (
     "qgcm_route_chain_seal_packed_host",
     "qgcm_tun_read_packed", "qgcm_frames_resolve", "qgcm_frames_unpack_cpu", "qgcm_route_chain_seal_frames_host",
     "qgcm_gro_resolve",
+    "qgcm_tun_open_offload", "qgcm_tun_read_gso", "qgcm_gso_resolve", "qgcm_gso_unpack_cpu",
+    "qgcm_route_chain_seal_gso_host",
 )
 
 QGCM_OK = 0
@@ -62,6 +64,9 @@ OVERHEAD = 28
 NO_PEER = 0xFFFFFFFF  # QGCM_NO_PEER: a packet no route resolves, an empty route-table entry
 TX, RX = 0, 1  # QGCM_TX / QGCM_RX
 PLUGIN_COMPRESSION, PLUGIN_ENCRYPTION = 1, 2  # QGCM_PLUGIN_*: per-peer plugin flags, the node's own mask
+GSO_PLAIN, GSO_CSUM, GSO_TCP4, GSO_UDP4 = 0, 1, 2, 3  # QGCM_GSO_*: the kinds of a super-frame table entry
+GSO_SEGS = 2048  # QGCM_GSO_SEGS: the most slots one entry names
+TUN_TSO4, TUN_USO = 1, 2  # QGCM_TUN_*: the offloads qgcm_tun_open_offload asks for
 GRO_SEGS = 64  # QGCM_GRO_SEGS: the most datagrams the kernel coalesces into one received buffer
 
 
@@ -140,6 +145,15 @@ class Frame(C.Structure):
     """qgcm_frame: {off (a multiple of 16), len}: packed[off, off + len) belongs to slot i -- 8 bytes."""
 
     _fields_ = [("off", C.c_uint32), ("len", C.c_uint32)]
+
+
+class GsoFrame(C.Structure):
+    """qgcm_gso_frame: {off, len, first, count, gso_size u16, hdr_len u16, l4_off u16, csum_off u16, kind, reserved}
+    -- 32 bytes."""
+
+    _fields_ = [("off", C.c_uint32), ("len", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32),
+                ("gso_size", C.c_uint16), ("hdr_len", C.c_uint16), ("l4_off", C.c_uint16), ("csum_off", C.c_uint16),
+                ("kind", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 _lib: C.CDLL | None = None
@@ -298,6 +312,12 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_route_chain_seal_frames_host.argtypes = [vp, vp, u64, vp, u64, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp]
     if hasattr(L, "qgcm_gro_resolve"):  # (older builds loaded by the A/B tools lack the fused receive)
         L.qgcm_gro_resolve.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, vp, vp, vp]
+    if hasattr(L, "qgcm_gso_resolve"):  # (older builds loaded by the A/B tools lack the super-frames)
+        L.qgcm_tun_open_offload.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz, u32]
+        L.qgcm_tun_read_gso.argtypes = [C.c_int, vp, u64, vp, u32, u32, C.c_int, vp]
+        L.qgcm_gso_resolve.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, vp, vp, vp]
+        L.qgcm_gso_unpack_cpu.argtypes = [vp, u64, vp, u32, u32, vp, u64, vp]
+        L.qgcm_route_chain_seal_gso_host.argtypes = [vp, vp, u64, vp, u32, u64, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

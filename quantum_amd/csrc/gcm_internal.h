@@ -443,6 +443,26 @@ struct GroResolveArgs {
     uint32_t net, mask, gateway;
 };
 hipError_t launch_gro_resolve(const GroResolveArgs &a, hipStream_t s);
+// TUN super-frames cut into slots and resolved (gso_kernels.hip; include/qgcm.h "TUN super-frames segmented on
+// routed batches"): every valid entry of the table into the slots it names, headers patched and checksums
+// computed, then what route_resolve_kernel<outgoing> does with each, one launch on s (the 16-byte path when stride
+// and arena allow it, else the dword path).  packed and frames are 16-B aligned, packed readable up to the 16-B
+// boundary behind packed_len; stride a multiple of 4, at least 8; n_frames <= n; the caller has checked the
+// arguments.  n == 0 or n_frames == 0 launches nothing.
+struct GsoArgs {
+    const uint8_t *packed;
+    uint64_t packed_len;
+    const qgcm_gso_frame *frames;  // 16-B aligned
+    uint32_t n_frames, n;
+    uint8_t *arena;
+    uint64_t stride;
+    uint32_t *lens, *peer;         // written for the slots an entry names (and the first slot of a void entry)
+    qgcm_desc *descs;              // 16-B aligned
+    const uint2 *table;
+    uint32_t cap_mask;
+    uint32_t net, mask, gateway, own_ip;
+};
+hipError_t launch_gso_resolve(const GsoArgs &a, hipStream_t s);
 // qgcm_send_plan_host plans on the device from this many packets on (QGCM_PLAN_DEVICE_MIN at qgcm_create): the
 // measured crossover -- 181 against 186 us at 65536, 319 against 993 us at 262144
 constexpr uint32_t kPlanDeviceMin = 65536;

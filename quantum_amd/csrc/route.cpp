@@ -20,6 +20,7 @@
 #include "frames_core.h"
 #include "gcm_internal.h"
 #include "gro_core.h"
+#include "gso_core.h"
 #include "pack_core.h"
 #include "send_plan_core.h"
 #include "train_core.h"
@@ -80,6 +81,12 @@ struct RouteState {
     uint8_t *d_frames = nullptr;
     size_t frames_cap = 0;
     std::vector<qgcm_frame> h_frames;
+
+    // the super-frame pipeline: a chunk's table and packed bytes on the device, the rebased table on the host
+    // (under pipe_mu, on `stream`)
+    uint8_t *d_gso = nullptr;
+    size_t gso_cap = 0;
+    std::vector<qgcm_gso_frame> h_gso;
 };
 
 RouteState *route_state_create() {
@@ -103,6 +110,7 @@ void route_state_destroy(RouteState *r) {
     hipFree(r->d_pack);
     hipFree(r->d_train);
     hipFree(r->d_frames);
+    hipFree(r->d_gso);
     if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
@@ -174,6 +182,41 @@ int frames_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, 
     a.gateway = r->net.gateway;
     a.own_ip = r->net.own_ip;
     return hip_rc(launch_frames_resolve(a, s));
+}
+
+// qgcm_gso_resolve: frames_resolve() for a table of super-frames; the table pointer is taken the same way.
+int gso_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gso_frame *d_frames, uint32_t n_frames,
+                uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens, uint32_t *d_peer, qgcm_desc *d_descs,
+                hipStream_t s) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || stride < 8 || n > QGCM_MAX_BATCH || n_frames > n) return QGCM_E_ARG;
+    if (n && (!d_packed || !d_frames || !d_arena || !d_lens || !d_peer || !d_descs)) return QGCM_E_ARG;
+    if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_frames & 15) || ((uintptr_t)d_arena & 3) || ((uintptr_t)d_lens & 3) ||
+        ((uintptr_t)d_peer & 3) || ((uintptr_t)d_descs & 15))
+        return QGCM_E_ARG;
+    std::lock_guard<std::mutex> g(r->mu);
+    if (!r->set) return QGCM_E_ARG;
+    if (n == 0 || n_frames == 0) return QGCM_OK;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    GsoArgs a{};
+    a.packed = d_packed;
+    a.packed_len = packed_len;
+    a.frames = d_frames;
+    a.n_frames = n_frames;
+    a.n = n;
+    a.arena = d_arena;
+    a.stride = stride;
+    a.lens = d_lens;
+    a.peer = d_peer;
+    a.descs = d_descs;
+    a.table = r->d_table;
+    a.cap_mask = r->cap_mask;
+    a.net = r->net.net;
+    a.mask = r->net.mask;
+    a.gateway = r->net.gateway;
+    a.own_ip = r->net.own_ip;
+    return hip_rc(launch_gso_resolve(a, s));
 }
 
 // qgcm_gro_resolve: resolve(ctx, false, ...) for a batch that is still in its coalesced buffers; the table pointer
@@ -802,6 +845,111 @@ int run_route_frames_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packe
     return dropped;
 }
 
+// Outgoing.pipeline for a batch that was read as super-frames (qgcm_tun_read_gso): run_route_frames_host with
+// gso_resolve_kernel in place of frames_resolve_kernel.  An entry names a run of slots, so chunks end at entry
+// boundaries, as run_route_gro_host's: entries [e0, e1), slots [c0, c0 + cn), packed bytes [lo, hi) -- every entry
+// is valid (the table is checked), so lo, a 16-B boundary, is the least off and hi the greatest end.  Per chunk
+// the span and the entries, rebased to the span and to the chunk's first slot, go up; chain, plan, train pack,
+// accounting and the copy back follow as in run_route_frames_host.
+int run_route_gso_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gso_frame *frames, uint32_t n_frames,
+                       uint64_t stride, uint32_t n, uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins, uint32_t *h_peer,
+                       uint8_t *h_status, TrainOut &tk) {
+    if (!ctx) return QGCM_E_ARG;
+    RouteState *r = ctx_route(ctx);
+    if ((stride & 3) || stride < 8 || n > QGCM_MAX_BATCH || n_frames > n || !h_nonces || (plugins & ~kAllPlugins)) return QGCM_E_ARG;
+    if (n && (!h_packed || !frames || !h_lens || !h_peer)) return QGCM_E_ARG;
+    if (!gso_table_ok(frames, n_frames, n, packed_len)) return QGCM_E_ARG;
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+    }
+    if (n == 0) return 0;
+    const bool gen = h_nonces == QGCM_NONCES_GENERATE;
+    std::lock_guard<std::mutex> pg(r->pipe_mu);
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
+        r->stream = nullptr;
+        return QGCM_E_HIP;
+    }
+    hipStream_t s = r->stream;
+    const uint32_t limit = (uint32_t)std::min<uint64_t>(kRouteChunk, std::max<uint64_t>(1, kRouteChunkBytes / stride));
+    struct Chunk {
+        uint32_t e0, e1, c0, cn;
+        uint64_t lo, hi;
+    };
+    std::vector<Chunk> chunks;
+    uint32_t max_cn = 0, max_ne = 0;
+    uint64_t max_span = 0;
+    for (uint32_t e = 0; e < n_frames;) {
+        Chunk c{e, e, frames[e].first, 0, UINT64_MAX, 0};
+        for (; e < n_frames; ++e) {
+            if (c.cn && (uint64_t)c.cn + frames[e].count > limit) break;
+            c.cn += frames[e].count;
+            c.lo = std::min<uint64_t>(c.lo, frames[e].off);
+            c.hi = std::max<uint64_t>(c.hi, (uint64_t)frames[e].off + frames[e].len);
+        }
+        c.e1 = e;
+        max_cn = std::max(max_cn, c.cn);
+        max_ne = std::max(max_ne, c.e1 - c.e0);
+        max_span = std::max(max_span, c.hi - c.lo);
+        chunks.push_back(c);
+    }
+    // side buffer of a chunk as in run_route_frames_host; the table (16-B aligned) and the packed bytes (16-B
+    // aligned, rounded up to 16 B) in a staging area of their own
+    const size_t o_desc = 0, o_lens = o_desc + 16ull * max_cn, o_peer = o_lens + 4ull * max_cn, o_non = o_peer + 4ull * max_cn,
+                 o_stat = o_non + 12ull * max_cn, o_bytes = (o_stat + max_cn + 15) & ~(size_t)15,
+                 o_work = o_bytes + 4 * (size_t)chain_work_lanes(max_cn), side = o_work + QGCM_CHAIN_WORK(max_cn);
+    const size_t o_packed = 32ull * max_ne, staging = o_packed + (size_t)((max_span + 15) & ~(uint64_t)15);
+    if (!grow(r->d_arena, r->arena_cap, (size_t)max_cn * stride) || !grow(r->d_side, r->side_cap, side) ||
+        !grow(r->d_gso, r->gso_cap, std::max<size_t>(staging, 16)) || !train_grow(r, tk, max_cn, stride))
+        return QGCM_E_NOMEM;
+    r->h_stat.resize(max_cn);
+    r->h_gso.resize(max_ne);
+    qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
+    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
+    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
+    uint8_t *d_non = r->d_side + o_non, *d_stat = r->d_side + o_stat;
+    uint32_t *d_bytes = reinterpret_cast<uint32_t *>(r->d_side + o_bytes);
+    qgcm_gso_frame *d_frames = reinterpret_cast<qgcm_gso_frame *>(r->d_gso);
+    uint8_t *d_packed = r->d_gso + o_packed;
+    int dropped = 0;
+    for (const Chunk &c : chunks) {
+        const uint32_t ne = c.e1 - c.e0, cn = c.cn, c0 = c.c0;
+        for (uint32_t j = 0; j < ne; ++j) {
+            r->h_gso[j] = frames[c.e0 + j];
+            r->h_gso[j].off -= (uint32_t)c.lo;
+            r->h_gso[j].first -= c0;
+        }
+        int rc = QGCM_OK;
+        if ((c.hi > c.lo && hipMemcpyAsync(d_packed, h_packed + c.lo, (size_t)(c.hi - c.lo), hipMemcpyHostToDevice, s) != hipSuccess) ||
+            hipMemcpyAsync(d_frames, r->h_gso.data(), 32ull * ne, hipMemcpyHostToDevice, s) != hipSuccess ||
+            (!gen && hipMemcpyAsync(d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, s) != hipSuccess))
+            rc = QGCM_E_HIP;
+        if (rc == QGCM_OK)
+            rc = gso_resolve(ctx, d_packed, c.hi - c.lo, d_frames, ne, cn, r->d_arena, stride, d_lens, d_peer, d_descs, s);
+        if (rc == QGCM_OK)
+            rc = run_chain(ctx, true, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, gen ? QGCM_NONCES_GENERATE : d_non,
+                           d_stat, d_bytes, r->d_side + o_work, s);
+        if (rc == QGCM_OK) rc = train_chunk(tk, ctx_max_keys(ctx), r->d_arena, stride, c0, cn, d_lens, d_peer, s);
+        if (rc == QGCM_OK) rc = account(ctx, QGCM_TX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
+        if (rc == QGCM_OK &&
+            (!train_copy_back(tk, s) || hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+             hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess))
+            rc = QGCM_E_HIP;
+        // every way out waits for the stream: the next call reuses the staging, and the caller its arrays
+        if (hipStreamSynchronize(s) != hipSuccess && rc == QGCM_OK) rc = QGCM_E_HIP;
+        if (rc != QGCM_OK) return rc;
+        train_rebase(tk, c0, cn);
+        for (uint32_t i = 0; i < cn; ++i) {
+            const bool ok = r->h_stat[i] == 1;
+            if (h_status) h_status[c0 + i] = ok ? 1 : 0;
+            dropped += !ok;
+        }
+    }
+    return dropped;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1117,6 +1265,29 @@ int qgcm_route_chain_seal_frames_host(qgcm_ctx *ctx, const uint8_t *h_packed, ui
     TrainOut tk{h_out, std::min<uint64_t>(out_cap, kTrainMaxCap), h_ptrains, h_order, out};
     if (!plan_limits_resolve(limits, &tk.lim)) return QGCM_E_ARG;
     return run_route_frames_host(ctx, h_packed, packed_len, frames, stride, n, h_lens, h_nonces, plugins, h_peer, h_status, tk);
+}
+
+int qgcm_gso_resolve(qgcm_ctx *ctx, const uint8_t *d_packed, uint64_t packed_len, const qgcm_gso_frame *d_frames, uint32_t n_frames,
+                     uint32_t n, uint8_t *d_arena, uint64_t stride, uint32_t *d_lens, uint32_t *d_peer, qgcm_desc *d_descs,
+                     void *stream) {
+    return gso_resolve(ctx, d_packed, packed_len, d_frames, n_frames, n, d_arena, stride, d_lens, d_peer, d_descs,
+                       (hipStream_t)stream);
+}
+
+int qgcm_gso_unpack_cpu(const uint8_t *packed, uint64_t packed_len, const qgcm_gso_frame *frames, uint32_t n_frames, uint32_t n,
+                        uint8_t *arena, uint64_t stride, uint32_t *lens) {
+    return gso_unpack_checked(packed, packed_len, frames, n_frames, n, arena, stride, lens);
+}
+
+int qgcm_route_chain_seal_gso_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gso_frame *frames,
+                                   uint32_t n_frames, uint64_t stride, uint32_t n, uint32_t *h_lens, const uint8_t *h_nonces,
+                                   uint32_t plugins, const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
+                                   uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order, uint64_t out[4]) {
+    if (!out || (n && (!h_out || !h_ptrains))) return QGCM_E_ARG;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    TrainOut tk{h_out, std::min<uint64_t>(out_cap, kTrainMaxCap), h_ptrains, h_order, out};
+    if (!plan_limits_resolve(limits, &tk.lim)) return QGCM_E_ARG;
+    return run_route_gso_host(ctx, h_packed, packed_len, frames, n_frames, stride, n, h_lens, h_nonces, plugins, h_peer, h_status, tk);
 }
 
 int qgcm_route_stats(qgcm_ctx *ctx, int dir, uint32_t peer, uint64_t out[4]) {

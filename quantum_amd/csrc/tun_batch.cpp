@@ -35,6 +35,7 @@
 
 #include "../../include/qgcm.h"
 #include "frames_core.h"
+#include "gso_core.h"
 #include "pack_core.h"
 
 namespace {
@@ -192,6 +193,60 @@ int uring_drain(Ring &r, int fd, uint8_t *arena, uint64_t stride, uint32_t first
 void set_name(ifreq *r, const char *name) {
     memset(r, 0, sizeof *r);
     if (name) memcpy(r->ifr_name, name, strnlen(name, IFNAMSIZ - 1));  // stays NUL-terminated (memset above)
+}
+
+// linux/if_tun.h before 6.2 lacks the UDP segmentation bits
+constexpr unsigned long kTunUso4 = 0x20, kTunUso6 = 0x40;
+
+// The entry that gives a frame's one slot the void-frame result: the PLAIN packet of length 0.
+qgcm_gso_frame gso_unsplit(uint32_t off, uint32_t first) {
+    qgcm_gso_frame f{};
+    f.off = off;
+    f.first = first;
+    f.count = 1;
+    f.kind = QGCM_GSO_PLAIN;
+    return f;
+}
+
+// The table entry of one read of `bytes` bytes at `vnet`: struct virtio_net_hdr (linux/virtio_net.h; the fields in
+// host order, as a TUN queue writes them without TUNSETVNETLE) -- flags, gso_type, hdr_len, gso_size, csum_start,
+// csum_offset -- then the IP packet, which lies at `off` of the packed area.  The header's hdr_len is the linear
+// part of the kernel's buffer, at times the whole frame: the TCP header length comes from the packet's data-offset
+// nibble.  A frame this does not split comes back as gso_unsplit; the caller runs the validity rule over the rest.
+qgcm_gso_frame gso_entry(const uint8_t *vnet, uint64_t bytes, uint32_t off, uint32_t first) {
+    constexpr uint8_t kNeedsCsum = 1, kGsoNone = 0, kGsoTcp4 = 1, kGsoUdpL4 = 5;
+    if (bytes < qgcm::kGsoVnetHdr) return gso_unsplit(off, first);
+    const uint8_t *pkt = vnet + qgcm::kGsoVnetHdr;
+    uint16_t gso_size, csum_start, csum_offset;
+    memcpy(&gso_size, vnet + 4, 2);
+    memcpy(&csum_start, vnet + 6, 2);
+    memcpy(&csum_offset, vnet + 8, 2);
+    qgcm_gso_frame f = gso_unsplit(off, first);
+    f.len = (uint32_t)(bytes - qgcm::kGsoVnetHdr);
+    const uint8_t type = vnet[1];
+    if (type == kGsoNone) {
+        if (vnet[0] & kNeedsCsum) {
+            f.kind = QGCM_GSO_CSUM;
+            f.l4_off = csum_start;
+            f.csum_off = csum_offset;
+        }
+        return f;
+    }
+    // (the ECN bit, 0x80, makes the type none of these)
+    if ((type != kGsoTcp4 && type != kGsoUdpL4) || f.len < 1 || pkt[0] >> 4 != 4) return gso_unsplit(off, first);
+    f.l4_off = csum_start;
+    f.gso_size = gso_size;
+    if (type == kGsoTcp4) {
+        if ((uint64_t)csum_start + 13 > f.len) return gso_unsplit(off, first);
+        f.kind = QGCM_GSO_TCP4;
+        f.hdr_len = (uint16_t)(csum_start + 4u * (pkt[csum_start + 12] >> 4));
+    } else {
+        f.kind = QGCM_GSO_UDP4;
+        f.hdr_len = (uint16_t)(csum_start + 8u);
+    }
+    if (f.hdr_len >= f.len || gso_size == 0) return gso_unsplit(off, first);
+    f.count = qgcm::gso_seg_count(f.len, f.hdr_len, gso_size);
+    return f;
 }
 
 }  // namespace
@@ -400,6 +455,111 @@ int qgcm_tun_read_packed(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_fram
         landed(n);
     }
     return done((int)got);
+}
+
+// qgcm_tun_open for a queue that hands over super-frames (include/qgcm.h "TUN super-frames segmented on routed
+// batches"): IFF_VNET_HDR, a virtio_net_hdr of 10 bytes, and the offloads the mask names.
+int qgcm_tun_open_offload(const char *name, int queues, int *fds, char *ifname_out, size_t ifname_len, uint32_t offloads) {
+    if (queues <= 0 || !fds || (offloads & ~(QGCM_TUN_TSO4 | QGCM_TUN_USO))) return -EINVAL;
+    unsigned long feat = offloads ? TUN_F_CSUM : 0;
+    if (offloads & QGCM_TUN_TSO4) feat |= TUN_F_TSO4;
+    if (offloads & QGCM_TUN_USO) feat |= kTunUso4 | kTunUso6;  // the kernel takes the two only as a pair
+    char dev[IFNAMSIZ] = {0};
+    if (name) strncpy(dev, name, IFNAMSIZ - 1);
+    for (int i = 0; i < queues; ++i) {
+        const int fd = open("/dev/net/tun", O_RDWR | O_CLOEXEC);
+        int err = fd < 0 ? errno : 0;
+        if (fd >= 0) {
+            ifreq r;
+            set_name(&r, dev);
+            r.ifr_flags = IFF_TUN | IFF_NO_PI | IFF_MULTI_QUEUE | IFF_VNET_HDR;
+            int hdr = (int)qgcm::kGsoVnetHdr;
+            if (ioctl(fd, TUNSETIFF, &r) != 0 || ioctl(fd, TUNSETVNETHDRSZ, &hdr) != 0 || ioctl(fd, TUNSETOFFLOAD, feat) != 0) {
+                err = errno;
+                close(fd);
+            } else {
+                memcpy(dev, r.ifr_name, IFNAMSIZ);  // later queues attach to the same device
+                dev[IFNAMSIZ - 1] = 0;
+                fds[i] = fd;
+            }
+        }
+        if (err) {
+            for (int j = 0; j < i; ++j) close(fds[j]);
+            return -err;
+        }
+    }
+    if (ifname_out && ifname_len) {
+        strncpy(ifname_out, dev, ifname_len - 1);
+        ifname_out[ifname_len - 1] = 0;
+    }
+    return 0;
+}
+
+// qgcm_tun_read_packed for a queue opened by qgcm_tun_open_offload: the same wait for the first frame and the same
+// drain (preadv2(RWF_NOWAIT) a frame; poll + read where that is refused or with QGCM_TUN_URING=-1).  A read goes to
+// the 10 bytes before the next 16-byte boundary that leaves them free, so the vnet header ends where the IP packet
+// starts, and is made only with kGsoRoom bytes of room from the boundary before it -- a super-frame is at most 65535
+// bytes behind its header -- and with QGCM_GSO_SEGS slots left.  One table entry a read, from the vnet header
+// (gso_entry below).
+int qgcm_tun_read_gso(int fd, uint8_t *packed, uint64_t packed_cap, qgcm_gso_frame *frames, uint32_t max_frames, uint32_t max_n,
+                      int timeout_ms, uint64_t out[3]) {
+    using qgcm::kGsoRoom;
+    using qgcm::kGsoVnetHdr;
+    if (out) out[0] = out[1] = out[2] = 0;
+    if (fd < 0 || !packed || !frames || packed_cap < kGsoRoom || max_n < QGCM_GSO_SEGS) return -1;
+    if (max_frames == 0) return 0;
+    pollfd p{fd, POLLIN, 0};
+    int pr;
+    do {
+        pr = poll(&p, 1, timeout_ms);
+    } while (pr < 0 && errno == EINTR);
+    if (pr < 0) return -1;
+    if (pr == 0) return 0;
+    // `off` is 32 bits: the area counts up to 4 GiB
+    const uint64_t cap = packed_cap < (1ull << 32) ? packed_cap : (1ull << 32);
+    uint32_t got = 0, named = 0, unsplit = 0;
+    uint64_t at = 16, end = 0;  // where the next IP packet goes; the end of the last one
+    auto done = [&](int rc) {
+        if (out && rc >= 0) out[0] = got, out[1] = end, out[2] = unsplit;
+        return rc;
+    };
+    static std::atomic<int> nowait_ok{1};
+    if (read_mode() == 2) nowait_ok.store(0, std::memory_order_relaxed);
+    while (got < max_frames && max_n - named >= QGCM_GSO_SEGS && at - 16 + kGsoRoom <= cap) {
+        uint8_t *dst = packed + at - kGsoVnetHdr;
+        const size_t room = (size_t)(kGsoRoom - 16 + kGsoVnetHdr);
+        ssize_t n;
+        if (nowait_ok.load(std::memory_order_relaxed)) {
+            iovec v{dst, room};
+            n = preadv2(fd, &v, 1, -1, RWF_NOWAIT);
+            if (n < 0 && (errno == EOPNOTSUPP || errno == EINVAL || errno == ENOSYS)) {
+                nowait_ok.store(0, std::memory_order_relaxed);
+                continue;
+            }
+        } else {
+            if (got) {  // drain without blocking: only what is already queued joins this batch
+                p.revents = 0;
+                do {
+                    pr = poll(&p, 1, 0);
+                } while (pr < 0 && errno == EINTR);
+                if (pr <= 0) break;
+            }
+            n = read(fd, dst, room);
+        }
+        if (n < 0) {
+            if (errno == EINTR) continue;
+            if (errno == EAGAIN || errno == EWOULDBLOCK) break;
+            return done(got ? (int)named : -1);
+        }
+        qgcm_gso_frame f = gso_entry(dst, (uint64_t)n, (uint32_t)at, named);
+        if (!qgcm::gso_valid(f, at + f.len, named + f.count)) f = gso_unsplit((uint32_t)at, named);
+        unsplit += f.kind == QGCM_GSO_PLAIN && f.len == 0;
+        frames[got++] = f;
+        named += f.count;
+        end = at + f.len;
+        at = (end + kGsoVnetHdr + 15) & ~(uint64_t)15;
+    }
+    return done((int)named);
 }
 
 // device/tun.go:60-63, batched: writes Raw[4 : 4 + lens[i]] of slots 0..n-1 (payload.Packet after

@@ -23,7 +23,9 @@ device/tun.go:60-63        Write, from delivered packets packed back to back on 
                            deliver_pack_cpu, tun_write_packed, route_chain_open_packed_host,
                            route_chain_open_gro_packed_host
 device/tun.go:51-57        Read, packed back to back and put into slots and resolved on the GPU -> tun_read_packed,
-                           frames_resolve, frames_unpack_cpu, route_chain_seal_frames_host
+                           frames_resolve, frames_unpack_cpu, route_chain_seal_frames_host; as TSO / USO super-frames
+                           cut into packets on the GPU -> tun_open_offload, tun_read_gso, gso_resolve, gso_unpack_cpu,
+                           route_chain_seal_gso_host
 """
 from __future__ import annotations
 
@@ -609,4 +611,65 @@ def route_chain_seal_frames_host(ctx, packed, packed_len: int, frames, stride: i
                                                       order.ctypes.data, out.ctypes.data)
     if rc < 0 and rc != _lib.QGCM_E_NOMEM:
         _lib.check(rc, "qgcm_route_chain_seal_frames_host")
+    return rc, ptrains[:int(out[1])], order[:int(out[3])], out
+
+
+# qgcm_gso_frame as a numpy record: a table is a contiguous array of these
+GSO_FRAME = [("off", "<u4"), ("len", "<u4"), ("first", "<u4"), ("count", "<u4"), ("gso_size", "<u2"), ("hdr_len", "<u2"),
+             ("l4_off", "<u2"), ("csum_off", "<u2"), ("kind", "<u4"), ("reserved", "<u4")]
+
+
+def tun_open_offload(name: bytes, queues: int, offloads: int):
+    """qgcm_tun_open_offload -> (rc, fds, ifname): rc 0 or -errno; `offloads` a mask of _lib.TUN_TSO4 / _lib.TUN_USO."""
+    fds, ifname = (C.c_int * queues)(), C.create_string_buffer(16)
+    rc = _lib.lib().qgcm_tun_open_offload(name, queues, fds, ifname, 16, offloads)
+    return rc, list(fds) if rc == 0 else [], ifname.value
+
+
+def tun_read_gso(fd: int, packed, frames, max_n: int, timeout_ms: int, out=None) -> int:
+    """qgcm_tun_read_gso into `packed` (a contiguous numpy uint8 array of at least 65536 + 16 bytes) and `frames` (a
+    numpy array of GSO_FRAME records, one per read at the most); `out` a numpy uint64 array of 3 ({entries, bytes
+    used, frames not split}) or None.  Returns the number of slots named, 0 on timeout, or -1."""
+    return _lib.lib().qgcm_tun_read_gso(fd, packed.ctypes.data, packed.size, frames.ctypes.data, len(frames), max_n,
+                                        timeout_ms, None if out is None else out.ctypes.data)
+
+
+def gso_resolve(ctx, packed, packed_len: int, frames, n_frames: int, n: int, arena, stride: int, lens, peer, descs,
+                stream=None) -> None:
+    """qgcm_gso_resolve on device tensors: `packed` uint8 (16-B aligned, its size rounded up to 16 B), `frames`
+    uint8 (32 n_frames bytes: GSO_FRAME records), `lens` / `peer` int32 (n), `descs` uint8 (16 n bytes);
+    chain_outgoing follows on the same stream."""
+    _lib.check(_lib.lib().qgcm_gso_resolve(ctx.handle, _ptr(packed), packed_len, _ptr(frames), n_frames, n, _ptr(arena),
+                                           stride, _ptr(lens), _ptr(peer), _ptr(descs), _stream_handle(stream)),
+               "qgcm_gso_resolve")
+
+
+def gso_unpack_cpu(packed, packed_len: int, frames, n: int, arena, stride: int, lens) -> None:
+    """qgcm_gso_unpack_cpu over numpy arrays: `packed` / `arena` uint8, `frames` GSO_FRAME records, `lens` uint32
+    (n).  Raises for a table that is not well-formed, with nothing written."""
+    _lib.check(_lib.lib().qgcm_gso_unpack_cpu(packed.ctypes.data, packed_len, frames.ctypes.data, len(frames), n,
+                                              arena.ctypes.data, stride, lens.ctypes.data), "qgcm_gso_unpack_cpu")
+
+
+def route_chain_seal_gso_host(ctx, packed, packed_len: int, frames, stride: int, n: int, lens, nonces, plugins: int,
+                              peer, status, out_buf, limits=None, ptrains=None, order=None):
+    """qgcm_route_chain_seal_gso_host: route_chain_seal_frames_host for what tun_read_gso left in `packed` and
+    `frames` (GSO_FRAME records naming n slots).  Returns as route_chain_seal_packed_host."""
+    import numpy as np
+
+    from .batch import GENERATE
+
+    if ptrains is None:
+        ptrains = np.zeros((max(1, n), 4), np.uint32)
+    if order is None:
+        order = np.zeros(max(1, n), np.uint32)
+    out = np.zeros(4, np.uint64)
+    np_ = _lib.NONCES_GENERATE if nonces is GENERATE else nonces
+    rc = _lib.lib().qgcm_route_chain_seal_gso_host(ctx.handle, packed.ctypes.data, packed_len, frames.ctypes.data,
+                                                   len(frames), stride, n, lens.ctypes.data, np_, plugins,
+                                                   _limits_ptr(limits), peer.ctypes.data,
+                                                   None if status is None else status.ctypes.data, out_buf.ctypes.data,
+                                                   out_buf.size, ptrains.ctypes.data, order.ctypes.data, out.ctypes.data)
+    if rc < 0 and rc != _lib.QGCM_E_NOMEM:
+        _lib.check(rc, "qgcm_route_chain_seal_gso_host")
     return rc, ptrains[:int(out[1])], order[:int(out[3])], out
