@@ -1073,7 +1073,7 @@ typedef struct qgcm_gso_frame {
     uint32_t first, count;        /* its first slot, its number of slots */
     uint16_t gso_size, hdr_len;   /* payload bytes a segment; IP + L4 header bytes (TCP4/UDP4) */
     uint16_t l4_off, csum_off;    /* csum_start (= IPv4 header length for TCP4/UDP4); csum_offset (CSUM only) */
-    uint32_t kind, reserved;      /* reserved = 0 */
+    uint32_t kind, reserved;      /* reserved: 0 on the read side, d_peer of `first` from qgcm_deliver_coalesce */
 } qgcm_gso_frame;                 /* 32 bytes, 16-B aligned */
 int qgcm_tun_open_offload(const char *name, int queues, int *fds, char *ifname_out, size_t ifname_len,
                           uint32_t offloads);
@@ -1090,6 +1090,103 @@ int qgcm_route_chain_seal_gso_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint6
                                    const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
                                    uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order,
                                    uint64_t out[4]);
+
+/* ---- delivered TCP segments coalesced on routed batches: GRO for the TUN write ---- */
+/* The mirror of the section above.  A TUN queue with IFF_VNET_HDR takes a virtio_net_hdr with GSO_TCPV4 on write as
+ * it hands one over on read, so a train of in-order TCP segments can go up as one frame: one write(2), one trip
+ * through the receiving stack.  Which neighbours may be merged is a comparison of headers and a ones'-complement
+ * sum over every byte; the merged frame goes up with NEEDS_CSUM and is trusted, so both checksums of every segment
+ * are verified first, and a segment that crossed the tunnel with a bad checksum reaches the receiver as it is.
+ *
+ * Packet i is delivered exactly as qgcm_deliver_pack defines it: d_status[i] == 1 and 4 + d_lens[i] <= stride
+ * (d_status == NULL: all 1); p = Raw[4 : 4 + L] is the packet.
+ *
+ * Candidate: a delivered packet with, every offset taken from p and bounded by L: L >= 40; p[0] >> 4 == 4;
+ * ihl = 4 * (p[0] & 15) in [20, 60]; IPv4 total length == L; protocol 6; (p[6:8] & 0xbfff) == 0 (no fragment,
+ * reserved bit clear, DF either way); doff = 4 * (p[ihl + 12] >> 4) in [20, 60]; hdr = ihl + doff and
+ * P = L - hdr >= 1; the low nibble of p[ihl + 12] zero; TCP flags with (flags & 0xf7) == 0x10 (ACK, optionally
+ * PSH, nothing else); the IPv4 header checksum field equal to the value recomputed over ihl bytes; the TCP
+ * checksum field equal to the value recomputed from scratch over pseudo-header (protocol 6, length L - ihl),
+ * header and payload, an odd length padded with a zero byte.  "Recomputed" is the value qgcm_gso_resolve would
+ * write for that packet; equality with it, not "sums to 0xffff", is the rule (a field of 0xffff where 0x0000 is
+ * recomputed is no candidate), so that segmentation and coalescing are exact inverses.
+ *
+ * link(i), 1 <= i < n: slots i - 1 and i are both candidates; d_peer equal; ihl and doff equal; every header
+ * byte equal except IP total length, IP id, IP checksum, TCP sequence number, the PSH bit and TCP checksum (so
+ * TOS, DF, TTL, addresses, IP options, ports, ack, window, urgent and TCP options match); seq_i == seq_{i-1} +
+ * P_{i-1} mod 2^32; id_i == id_{i-1} + 1 mod 2^16; PSH clear on i - 1.  eq(i) = link(i) and P_i == P_{i-1};
+ * lt(i) = link(i) and P_i < P_{i-1}; both false at i = 0 and i = n.  Adjacency is by slot: a dropped slot ends a
+ * run as a packet of another flow does.
+ *
+ * Frames.  A stretch is a maximal run under eq, head h, j = i - h.  m = min(QGCM_COALESCE_SEGS, (65535 - hdr) / P).
+ * Members of a stretch with equal j / m form one frame (the send plan's cut: no sequential walk).  Slot t is a
+ * tail when lt(t) && !eq(t + 1) && !lt(t - 1) and the frame that ends at t - 1 has fewer than m members; it joins
+ * that frame as its last member.  Three strictly falling sizes in a row merge only the first two: the rule stays
+ * local.  A frame of one member is a PLAIN entry.  Every delivered packet appears in exactly one entry, in slot
+ * order: no flow is reordered.
+ *
+ * Output: a packed area and a qgcm_gso_frame table in the layout qgcm_tun_read_gso produces.  Entry k's IP packet
+ * starts at off_k, a multiple of 16, off_0 = 16; its 10-byte virtio_net_hdr lies in [off_k - 10, off_k), bytes
+ * [off_k - 16, off_k - 10) are zero, the packet is zero-padded to 16 bytes, off_{k+1} = off_k + round16(len_k) + 16.
+ *   PLAIN entry:     kind QGCM_GSO_PLAIN, ten zero bytes of vnet header, the packet verbatim, count 1, the other
+ *                    16-bit fields 0.
+ *   Coalesced entry: (c >= 2 members) kind QGCM_GSO_TCP4, gso_size the head's P, hdr_len = hdr, l4_off = ihl,
+ *                    csum_off = 16, count = c.  The packet is the head's hdr bytes, then the members' payloads back
+ *                    to back.  The header is the head's with: total length hdr + sum of P; the IPv4 checksum
+ *                    recomputed; PSH taken from the last member; in the TCP checksum field the folded,
+ *                    uncomplemented ones'-complement sum of the pseudo-header (source, destination, 6, doff + sum
+ *                    of P), which is what NEEDS_CSUM expects.  The vnet header, host byte order: flags 1, gso_type
+ *                    1 (TCPV4), hdr_len, gso_size, csum_start ihl, csum_offset 16.
+ *   Every entry:     `first` the first member's slot, `reserved` d_peer of that slot.
+ * counts[4] = {entries, bytes = the end of the last entry, coalesced entries, delivered packets}; bytes is the
+ * full need even when it does not fit.  An entry whose region [off - 16, off + round16(len)) passes packed_cap is
+ * not copied and gets off = 0xffffffff; such entries form a suffix.  Every byte of [0, bytes) that fits is
+ * determined; everything behind it is untouched; table entries past counts[0] are unspecified.
+ * On any input no byte of a slot at or past 4 + L has any effect.  Loads are whole aligned dwords (16-byte pieces
+ * on the 16-byte path) that hold a byte below 4 + L: the bytes up to that dword's (that piece's) end, which lies
+ * inside the slot because stride is a multiple of 4 (of 16), are loaded and masked off, and nothing behind it is
+ * read.  Nothing at or past packed_cap is written, nothing past entry n of the table is written.
+ *
+ * qgcm_deliver_coalesce: device arrays, asynchronous on stream, no context state, no host synchronisation between
+ * its launches, calls on several streams may run at once.  Alignments as qgcm_deliver_pack's (d_frames, n entries,
+ * 16-B aligned; d_counts four uint64, 8-B aligned; d_work qgcm_deliver_coalesce_work(n) bytes, 16-B aligned, the
+ * call's own until it has run); a stride that is a multiple of 16 under a 16-B-aligned arena takes the 16-byte
+ * path, anything else the dword path.  n == 0: counts = {0, 0, 0, 0}, nothing else launched.  QGCM_E_ARG as
+ * qgcm_deliver_pack.
+ * qgcm_deliver_coalesce_cpu: the same contract for host arrays (no alignment asked), by the host: the yardstick,
+ * and the path of a worker on qgcm_route_chain_open_host.
+ *
+ * qgcm_tun_write_gso: for a queue from qgcm_tun_open_offload (any `offloads`, 0 included).  The whole table is
+ * checked first: every entry off >= 16, off % 16 == 0, off + len <= packed_len, kind PLAIN or TCP4, a TCP4 entry
+ * valid by the rule of the section above apart from `first`; else -1 with nothing written.  Then
+ * packed[off - 10, off + len) of each entry is written, in order; EINTR is retried; a TCP4 entry the kernel
+ * refuses with EINVAL is cut on the host (qgcm_gso_unpack_cpu's segmentation) and written packet by packet behind
+ * zero vnet headers; any other refusal ends the batch as in qgcm_tun_write_packed.  Returns the entries written,
+ * or -1 when none was; out (may be NULL) = {entries, packets, entries that fell back}.
+ *
+ * qgcm_route_chain_open_coalesced_host / qgcm_route_chain_open_gro_coalesced_host: the two ..._packed_host
+ * pipelines with the pack's launch replaced.  Chunks, order, accounting, QGCM_E_NOMEM and the rebasing of `off`
+ * and `first` are those of the packed forms; the device area of a chunk is cn * (round16(stride) + 16) bytes; runs
+ * do not cross a chunk edge: the result is qgcm_deliver_coalesce_cpu applied chunk by chunk, the chunks' areas
+ * one behind the other.  out[5] = {packets processed, entries, bytes, coalesced entries, delivered packets}. */
+#define QGCM_COALESCE_SEGS 64u
+uint64_t qgcm_deliver_coalesce_work(uint32_t n);
+int qgcm_deliver_coalesce(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+                          const uint32_t *d_peer, const uint8_t *d_status, uint8_t *d_packed, uint64_t packed_cap,
+                          qgcm_gso_frame *d_frames, uint64_t *d_counts, void *d_work, void *stream);
+int qgcm_deliver_coalesce_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
+                              const uint32_t *peer, const uint8_t *status, uint8_t *packed, uint64_t packed_cap,
+                              qgcm_gso_frame *frames, uint64_t counts[4]);
+int qgcm_tun_write_gso(int fd, const uint8_t *packed, uint64_t packed_len, const qgcm_gso_frame *frames, uint32_t m,
+                       uint64_t out[3]);
+int qgcm_route_chain_open_coalesced_host(qgcm_ctx *ctx, const uint8_t *h_arena, uint64_t stride, uint32_t n,
+                                         uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
+                                         uint8_t *h_out, uint64_t out_cap, qgcm_gso_frame *h_frames, uint64_t out[5]);
+int qgcm_route_chain_open_gro_coalesced_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
+                                             const qgcm_gro_buf *bufs, uint32_t n_bufs, uint64_t stride, uint32_t n,
+                                             uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
+                                             uint8_t *h_out, uint64_t out_cap, qgcm_gso_frame *h_frames,
+                                             uint64_t out[5]);
 
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19

@@ -52,6 +52,8 @@ EXPORTS = (
     "qgcm_gro_resolve",
     "qgcm_tun_open_offload", "qgcm_tun_read_gso", "qgcm_gso_resolve", "qgcm_gso_unpack_cpu",
     "qgcm_route_chain_seal_gso_host",
+    "qgcm_deliver_coalesce_work", "qgcm_deliver_coalesce", "qgcm_deliver_coalesce_cpu", "qgcm_tun_write_gso",
+    "qgcm_route_chain_open_coalesced_host", "qgcm_route_chain_open_gro_coalesced_host",
 )
 
 QGCM_OK = 0
@@ -318,6 +320,14 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_gso_resolve.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, vp, vp, vp]
         L.qgcm_gso_unpack_cpu.argtypes = [vp, u64, vp, u32, u32, vp, u64, vp]
         L.qgcm_route_chain_seal_gso_host.argtypes = [vp, vp, u64, vp, u32, u64, u32, vp, vp, u32, vp, vp, vp, vp, u64, vp, vp, vp]
+    if hasattr(L, "qgcm_deliver_coalesce"):  # (older builds loaded by the A/B tools lack the coalescing)
+        L.qgcm_deliver_coalesce_work.argtypes = [u32]
+        L.qgcm_deliver_coalesce_work.restype = u64
+        L.qgcm_deliver_coalesce.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, u64, vp, vp, vp, vp]
+        L.qgcm_deliver_coalesce_cpu.argtypes = [vp, u64, u32, vp, vp, vp, vp, u64, vp, vp]
+        L.qgcm_tun_write_gso.argtypes = [C.c_int, vp, u64, vp, u32, vp]
+        L.qgcm_route_chain_open_coalesced_host.argtypes = [vp, vp, u64, u32, vp, u32, vp, vp, vp, u64, vp, vp]
+        L.qgcm_route_chain_open_gro_coalesced_host.argtypes = [vp, vp, u64, vp, u32, u64, u32, vp, u32, vp, vp, vp, u64, vp, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

@@ -397,6 +397,14 @@ uint64_t deliver_pack_work_bytes(uint32_t n);
 hipError_t launch_deliver_pack(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens, const uint32_t *peer,
                                const uint8_t *status, uint8_t *packed, uint64_t packed_cap, qgcm_pack_rec *recs,
                                uint64_t *counts, void *work, hipStream_t s);
+// Delivered TCP segments coalesced into super-frames (coalesce_kernels.hip; include/qgcm.h "delivered TCP segments
+// coalesced on routed batches"): classify, the two scans and the copy on s (the 16-byte path when stride and
+// arena allow it, else the dword path); work: deliver_coalesce_work_bytes(n) bytes, 16-B aligned; the caller has
+// checked the arguments.  n == 0 writes counts = {0, 0, 0, 0} and launches nothing.
+uint64_t deliver_coalesce_work_bytes(uint32_t n);
+hipError_t launch_deliver_coalesce(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens, const uint32_t *peer,
+                                   const uint8_t *status, uint8_t *packed, uint64_t packed_cap, qgcm_gso_frame *frames,
+                                   uint64_t *counts, void *work, hipStream_t s);
 // The trains of a plan packed back to back (train_kernels.hip; include/qgcm.h "planned trains packed on routed
 // batches"): tile sums, spine, emit and the copy on s (the 16-byte path when stride and arena allow it, else the
 // dword path); m and t are read from plan_counts on the device; work: train_pack_work_bytes(n) bytes, 16-B

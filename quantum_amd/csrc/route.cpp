@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/qgcm.h"
+#include "coalesce_core.h"
 #include "frames_core.h"
 #include "gcm_internal.h"
 #include "gro_core.h"
@@ -389,18 +390,26 @@ struct PackOut {
     uint64_t *d_counts = nullptr;
     void *d_work = nullptr;
     uint8_t *d_packed = nullptr;
-    uint64_t h_counts[2] = {0, 0};
+    uint64_t h_counts[4] = {0, 0, 0, 0};
+    // the coalesced pipelines (include/qgcm.h "delivered TCP segments coalesced on routed batches"): a table of
+    // super-frames in place of h_recs, out = {packets, entries, bytes, coalesced entries, delivered packets}
+    qgcm_gso_frame *h_frames = nullptr;
+    qgcm_gso_frame *d_frames = nullptr;
+    uint64_t coalesced = 0, delivered = 0;
 };
 
-inline uint64_t pack_area_bytes(uint32_t cn, uint64_t stride) {
-    return std::min<uint64_t>((uint64_t)cn * ((stride + 15) & ~(uint64_t)15), kPackMaxCap);
+// the device area of a chunk: every record (every entry behind its lead) fits
+inline uint64_t pack_area_bytes(const PackOut &pk, uint32_t cn, uint64_t stride) {
+    return std::min<uint64_t>((uint64_t)cn * (((stride + 15) & ~(uint64_t)15) + (pk.h_frames ? kCoLead : 0u)), kPackMaxCap);
 }
 
 // recs (16-B aligned first), counts, the scan's work area, the packed bytes (16-B aligned)
 bool pack_grow(RouteState *r, PackOut &pk, uint32_t max_cn, uint64_t stride) {
-    const size_t o_counts = 16ull * max_cn, o_work = o_counts + 16, o_packed = o_work + (size_t)deliver_pack_work_bytes(max_cn);
-    if (!grow(r->d_pack, r->pack_cap, o_packed + std::max<size_t>((size_t)pack_area_bytes(max_cn, stride), 16))) return false;
+    const size_t o_counts = (pk.h_frames ? 32ull : 16ull) * max_cn, o_work = o_counts + (pk.h_frames ? 32 : 16),
+                 o_packed = o_work + (size_t)(pk.h_frames ? deliver_coalesce_work_bytes(max_cn) : deliver_pack_work_bytes(max_cn));
+    if (!grow(r->d_pack, r->pack_cap, o_packed + std::max<size_t>((size_t)pack_area_bytes(pk, max_cn, stride), 16))) return false;
     pk.d_recs = reinterpret_cast<qgcm_pack_rec *>(r->d_pack);
+    pk.d_frames = reinterpret_cast<qgcm_gso_frame *>(r->d_pack);
     pk.d_counts = reinterpret_cast<uint64_t *>(r->d_pack + o_counts);
     pk.d_work = r->d_pack + o_work;
     pk.d_packed = r->d_pack + o_packed;
@@ -411,16 +420,23 @@ bool pack_grow(RouteState *r, PackOut &pk, uint32_t max_cn, uint64_t stride) {
 // (out written) when the chunk's bytes do not fit behind the fill position: nothing of it is accounted or copied.
 int pack_chunk(PackOut &pk, const uint8_t *d_arena, uint64_t stride, uint32_t c0, uint32_t cn, const uint32_t *d_lens,
                const uint32_t *d_peer, const uint8_t *d_stat, hipStream_t s) {
-    if (launch_deliver_pack(d_arena, stride, cn, d_lens, d_peer, d_stat, pk.d_packed, pack_area_bytes(cn, stride), pk.d_recs,
-                            pk.d_counts, pk.d_work, s) != hipSuccess ||
-        hipMemcpyAsync(pk.h_counts, pk.d_counts, 16, hipMemcpyDeviceToHost, s) != hipSuccess)
+    const uint64_t area = pack_area_bytes(pk, cn, stride);
+    const hipError_t e = pk.h_frames ? launch_deliver_coalesce(d_arena, stride, cn, d_lens, d_peer, d_stat, pk.d_packed, area,
+                                                               pk.d_frames, pk.d_counts, pk.d_work, s)
+                                     : launch_deliver_pack(d_arena, stride, cn, d_lens, d_peer, d_stat, pk.d_packed, area,
+                                                           pk.d_recs, pk.d_counts, pk.d_work, s);
+    if (e != hipSuccess || hipMemcpyAsync(pk.h_counts, pk.d_counts, pk.h_frames ? 32 : 16, hipMemcpyDeviceToHost, s) != hipSuccess)
         return QGCM_E_HIP;
     if (hipStreamSynchronize(s) != hipSuccess || pk.h_counts[0] > cn) return QGCM_E_HIP;
     pk.out[0] = c0;
     pk.out[1] = pk.m;
     pk.out[2] = pk.fill;
+    if (pk.h_frames) {
+        pk.out[3] = pk.coalesced;
+        pk.out[4] = pk.delivered;
+    }
     // a chunk whose records did not all fit the device area (slots of more than 4 GiB) cannot be delivered
-    if (pk.h_counts[1] > pack_area_bytes(cn, stride) || pk.fill + pk.h_counts[1] > pk.out_cap) return QGCM_E_NOMEM;
+    if (pk.h_counts[1] > area || pk.fill + pk.h_counts[1] > pk.out_cap) return QGCM_E_NOMEM;
     return QGCM_OK;
 }
 
@@ -428,7 +444,8 @@ int pack_chunk(PackOut &pk, const uint8_t *d_arena, uint64_t stride, uint32_t c0
 bool pack_copy_back(PackOut &pk, hipStream_t s) {
     const uint64_t m = pk.h_counts[0], bytes = pk.h_counts[1];
     return (!bytes || hipMemcpyAsync(pk.h_out + pk.fill, pk.d_packed, (size_t)bytes, hipMemcpyDeviceToHost, s) == hipSuccess) &&
-           (!m || hipMemcpyAsync(pk.h_recs + pk.m, pk.d_recs, 16ull * m, hipMemcpyDeviceToHost, s) == hipSuccess);
+           (!m || (pk.h_frames ? hipMemcpyAsync(pk.h_frames + pk.m, pk.d_frames, 32ull * m, hipMemcpyDeviceToHost, s)
+                               : hipMemcpyAsync(pk.h_recs + pk.m, pk.d_recs, 16ull * m, hipMemcpyDeviceToHost, s)) == hipSuccess);
 }
 
 // ... and, once they have arrived, rebased: `off` by the fill position, `slot` by the chunk's first slot
@@ -436,14 +453,23 @@ void pack_rebase(PackOut &pk, uint32_t c0, uint32_t cn) {
     const uint64_t m = pk.h_counts[0];
     if (pk.fill || c0)
         for (uint64_t k = pk.m; k < pk.m + m; ++k) {
-            pk.h_recs[k].off += (uint32_t)pk.fill;
-            pk.h_recs[k].slot += c0;
+            if (pk.h_frames) {
+                pk.h_frames[k].off += (uint32_t)pk.fill;
+                pk.h_frames[k].first += c0;
+            } else {
+                pk.h_recs[k].off += (uint32_t)pk.fill;
+                pk.h_recs[k].slot += c0;
+            }
         }
     pk.m += m;
     pk.fill += pk.h_counts[1];
     pk.out[0] = (uint64_t)c0 + cn;
     pk.out[1] = pk.m;
     pk.out[2] = pk.fill;
+    if (pk.h_frames) {
+        pk.out[3] = pk.coalesced += pk.h_counts[2];
+        pk.out[4] = pk.delivered += pk.h_counts[3];
+    }
 }
 
 // The copy back of the packed outgoing pipeline (include/qgcm.h "planned trains packed on routed batches"): where
@@ -1212,6 +1238,45 @@ int qgcm_route_chain_open_gro_packed_host(qgcm_ctx *ctx, const uint8_t *h_packed
     if (!out || (n && (!h_out || !h_recs))) return QGCM_E_ARG;
     out[0] = out[1] = out[2] = 0;
     PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), h_recs, out};
+    return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, nullptr, stride, n, h_lens, h_peer, h_status, true,
+                              plugins, &pk);
+}
+
+uint64_t qgcm_deliver_coalesce_work(uint32_t n) { return deliver_coalesce_work_bytes(n); }
+
+int qgcm_deliver_coalesce(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, uint32_t n, const uint32_t *d_lens,
+                          const uint32_t *d_peer, const uint8_t *d_status, uint8_t *d_packed, uint64_t packed_cap,
+                          qgcm_gso_frame *d_frames, uint64_t *d_counts, void *d_work, void *stream) {
+    if (!ctx || n > QGCM_MAX_BATCH || (stride & 3) || packed_cap > kPackMaxCap || !d_counts) return QGCM_E_ARG;
+    if (n && (!d_arena || !d_lens || !d_peer || !d_packed || !d_frames || !d_work || stride == 0)) return QGCM_E_ARG;
+    if (((uintptr_t)d_arena & 3) || ((uintptr_t)d_lens & 3) || ((uintptr_t)d_peer & 3) || ((uintptr_t)d_packed & 15) ||
+        ((uintptr_t)d_frames & 15) || ((uintptr_t)d_counts & 7) || ((uintptr_t)d_work & 15))
+        return QGCM_E_ARG;
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
+    return hip_rc(launch_deliver_coalesce(d_arena, stride, n, d_lens, d_peer, d_status, d_packed, packed_cap, d_frames,
+                                          d_counts, d_work, (hipStream_t)stream));
+}
+
+int qgcm_route_chain_open_coalesced_host(qgcm_ctx *ctx, const uint8_t *h_arena, uint64_t stride, uint32_t n,
+                                         uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
+                                         uint8_t *h_out, uint64_t out_cap, qgcm_gso_frame *h_frames, uint64_t out[5]) {
+    if (!out || (n && (!h_out || !h_frames))) return QGCM_E_ARG;
+    out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+    PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), nullptr, out};
+    pk.h_frames = h_frames;
+    return run_route_host(ctx, false, const_cast<uint8_t *>(h_arena), stride, n, h_lens, nullptr, h_peer, h_status, true,
+                          plugins, &pk);
+}
+
+int qgcm_route_chain_open_gro_coalesced_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len,
+                                             const qgcm_gro_buf *bufs, uint32_t n_bufs, uint64_t stride, uint32_t n,
+                                             uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
+                                             uint8_t *h_out, uint64_t out_cap, qgcm_gso_frame *h_frames,
+                                             uint64_t out[5]) {
+    if (!out || (n && (!h_out || !h_frames))) return QGCM_E_ARG;
+    out[0] = out[1] = out[2] = out[3] = out[4] = 0;
+    PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), nullptr, out};
+    pk.h_frames = h_frames;
     return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, nullptr, stride, n, h_lens, h_peer, h_status, true,
                               plugins, &pk);
 }

@@ -32,8 +32,10 @@
 #include <unistd.h>
 
 #include <atomic>
+#include <vector>
 
 #include "../../include/qgcm.h"
+#include "coalesce_core.h"
 #include "frames_core.h"
 #include "gso_core.h"
 #include "pack_core.h"
@@ -250,6 +252,39 @@ qgcm_gso_frame gso_entry(const uint8_t *vnet, uint64_t bytes, uint32_t off, uint
 }
 
 }  // namespace
+
+namespace qgcm {
+
+// A valid TCP4 entry cut on the host (gso_core.h's segmentation) and written packet by packet, each behind a zero
+// vnet header.  Returns the packets written: f.count, or fewer when a write failed (0 when the segments' memory
+// could not be had: nothing is thrown across the C entry point).
+int tun_write_gso_cut(int fd, const uint8_t *packed, const qgcm_gso_frame &f) {
+    qgcm_gso_frame g = f;
+    g.first = 0;
+    const uint64_t stride = (kGsoPacketStart + g.hdr_len + g.gso_size + 3) & ~(uint64_t)3;
+    std::vector<uint8_t> arena;
+    std::vector<uint32_t> lens;
+    try {
+        arena.resize((size_t)(stride * g.count));
+        lens.resize(g.count);
+    } catch (...) {
+        return 0;  // no memory for the segments: nothing written, the caller's batch ends here
+    }
+    gso_unpack_entry_cpu(packed, g, arena.data(), stride, lens.data());
+    static const uint8_t zeros[kGsoVnetHdr] = {0};
+    uint32_t k = 0;
+    while (k < g.count) {
+        const iovec iov[2] = {{const_cast<uint8_t *>(zeros), sizeof zeros}, {arena.data() + k * stride + kGsoPacketStart, lens[k]}};
+        if (writev(fd, iov, 2) < 0) {
+            if (errno == EINTR) continue;
+            break;
+        }
+        ++k;
+    }
+    return (int)k;
+}
+
+}  // namespace qgcm
 
 extern "C" {
 
@@ -594,6 +629,35 @@ int qgcm_tun_write_packed(int fd, const uint8_t *packed, uint64_t packed_len, co
             break;
         }
         ++done;
+    }
+    return done || m == 0 ? (int)done : -1;
+}
+
+// qgcm_tun_write_slots for a coalesced batch (include/qgcm.h "delivered TCP segments coalesced on routed batches"):
+// packed[off - 10, off + len) of entries 0..m-1 in order, vnet header and packet in one write.  The whole table is
+// checked before the first write.  A TCP4 entry the kernel refuses with EINVAL (a queue that does not take the
+// offload) is cut on the host and written packet by packet; any other refusal ends the batch there.
+int qgcm_tun_write_gso(int fd, const uint8_t *packed, uint64_t packed_len, const qgcm_gso_frame *frames, uint32_t m,
+                       uint64_t out[3]) {
+    if (out) out[0] = out[1] = out[2] = 0;
+    if (fd < 0 || (m && (!packed || !frames)) || !qgcm::co_table_ok(frames, m, packed_len)) return -1;
+    uint32_t done = 0;
+    uint64_t packets = 0, fell_back = 0;
+    while (done < m) {
+        const qgcm_gso_frame &f = frames[done];
+        const ssize_t w = write(fd, packed + f.off - qgcm::kGsoVnetHdr, (size_t)f.len + qgcm::kGsoVnetHdr);
+        if (w < 0) {
+            if (errno == EINTR) continue;
+            if (errno != EINVAL || f.kind != QGCM_GSO_TCP4 || qgcm::tun_write_gso_cut(fd, packed, f) != (int)f.count) break;
+            ++fell_back;
+        }
+        packets += f.count;
+        ++done;
+    }
+    if (out) {
+        out[0] = done;
+        out[1] = packets;
+        out[2] = fell_back;
     }
     return done || m == 0 ? (int)done : -1;
 }

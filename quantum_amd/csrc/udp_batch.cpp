@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/qgcm.h"
+#include "coalesce_core.h"
 #include "gro_core.h"
 #include "pack_core.h"
 #include "train_core.h"
@@ -581,6 +582,25 @@ int qgcm_deliver_pack_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, con
     if (n > QGCM_MAX_BATCH || (stride & 3) || packed_cap > qgcm::kPackMaxCap || !counts) return QGCM_E_ARG;
     if (n && (!arena || !lens || !peer || !packed || !recs || stride == 0)) return QGCM_E_ARG;
     qgcm::deliver_pack_cpu(arena, stride, n, lens, peer, status, packed, packed_cap, recs, counts);
+    return QGCM_OK;
+}
+
+// The delivered TCP segments of an opened batch coalesced by the host (coalesce_core.h; the contract of
+// qgcm_deliver_coalesce, no alignment asked): what a worker on qgcm_route_chain_open_host hands to
+// qgcm_tun_write_gso.
+int qgcm_deliver_coalesce_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens, const uint32_t *peer,
+                              const uint8_t *status, uint8_t *packed, uint64_t packed_cap, qgcm_gso_frame *frames,
+                              uint64_t counts[4]) {
+    if (n > QGCM_MAX_BATCH || (stride & 3) || packed_cap > qgcm::kPackMaxCap || !counts) return QGCM_E_ARG;
+    if (n && (!arena || !lens || !peer || !packed || !frames || stride == 0)) return QGCM_E_ARG;
+    std::vector<uint32_t> work;
+    try {
+        work.resize(2 * (size_t)n);
+    } catch (...) {
+        return QGCM_E_NOMEM;
+    }
+    qgcm::deliver_coalesce_cpu(arena, stride, n, lens, peer, status, packed, packed_cap, frames, counts, work.data(),
+                               work.data() + n);
     return QGCM_OK;
 }
 

@@ -673,3 +673,85 @@ def route_chain_seal_gso_host(ctx, packed, packed_len: int, frames, stride: int,
     if rc < 0 and rc != _lib.QGCM_E_NOMEM:
         _lib.check(rc, "qgcm_route_chain_seal_gso_host")
     return rc, ptrains[:int(out[1])], order[:int(out[3])], out
+
+
+COALESCE_NO_ROOM = 0xFFFFFFFF  # `off` of an entry whose region did not fit below packed_cap
+COALESCE_SEGS = 64             # QGCM_COALESCE_SEGS: the most segments of one coalesced entry
+
+
+def deliver_coalesce_work(n: int, device="cuda"):
+    """A work area for a deliver_coalesce call of n packets (qgcm_deliver_coalesce_work(n) bytes; torch allocations
+    are 16-B aligned)."""
+    import torch
+
+    return torch.empty(int(_lib.lib().qgcm_deliver_coalesce_work(n)), dtype=torch.uint8, device=device)
+
+
+def deliver_coalesce(ctx, arena, stride: int, n: int, lens, peer, status, packed, packed_cap: int, frames, counts, work,
+                     stream=None) -> None:
+    """qgcm_deliver_coalesce after chain_incoming on the same stream: `lens` / `peer` int32 (n), `status` uint8 (n)
+    or None, `packed` uint8 (16-B aligned), `frames` uint8 (32 n bytes: GSO_FRAME records), `counts` int64 (4:
+    entries, bytes, coalesced entries, delivered packets), `work` from deliver_coalesce_work(n)."""
+    _lib.check(_lib.lib().qgcm_deliver_coalesce(ctx.handle, _ptr(arena), stride, n, _ptr(lens), _ptr(peer), _ptr(status),
+                                                _ptr(packed), packed_cap, _ptr(frames), _ptr(counts), _ptr(work),
+                                                _stream_handle(stream)), "qgcm_deliver_coalesce")
+
+
+def deliver_coalesce_cpu(arena, stride: int, n: int, lens, peer, status, packed, frames=None):
+    """qgcm_deliver_coalesce_cpu over numpy arrays: `arena` / `packed` uint8 (packed_cap = packed.size), `lens` /
+    `peer` uint32 (n), `status` uint8 (n) or None -> (frames[:entries] GSO_FRAME records, counts a uint64 array of
+    4: entries, bytes (the full need), coalesced entries, delivered packets).  `packed` is written in place."""
+    import numpy as np
+
+    if frames is None:
+        frames = np.zeros(max(1, n), GSO_FRAME)
+    counts = np.zeros(4, np.uint64)
+    _lib.check(_lib.lib().qgcm_deliver_coalesce_cpu(arena.ctypes.data, stride, n, lens.ctypes.data, peer.ctypes.data,
+                                                    None if status is None else status.ctypes.data, packed.ctypes.data,
+                                                    packed.size, frames.ctypes.data, counts.ctypes.data),
+               "qgcm_deliver_coalesce_cpu")
+    return frames[:int(counts[0])], counts
+
+
+def tun_write_gso(fd: int, packed, packed_len: int, frames, out=None) -> int:
+    """qgcm_tun_write_gso: vnet header and packet of every entry of `frames` (GSO_FRAME records) to a queue from
+    tun_open_offload, in order; `out` a numpy uint64 array of 3 ({entries, packets, entries that fell back}) or
+    None.  Returns the entries written or -1."""
+    return _lib.lib().qgcm_tun_write_gso(fd, packed.ctypes.data, packed_len, frames.ctypes.data, len(frames),
+                                         None if out is None else out.ctypes.data)
+
+
+def route_chain_open_coalesced_host(ctx, arena_ptr: int, stride: int, n: int, lens, plugins: int, peer, status, out_buf,
+                                    frames=None):
+    """qgcm_route_chain_open_coalesced_host: route_chain_open_packed_host whose delivered packets come back
+    coalesced -> (rc, frames[:entries], out): rc the number of drops or QGCM_E_NOMEM, frames GSO_FRAME records,
+    out = {packets fully processed, entries, bytes of out_buf used, coalesced entries, delivered packets}."""
+    import numpy as np
+
+    if frames is None:
+        frames = np.zeros(max(1, n), GSO_FRAME)
+    out = np.zeros(5, np.uint64)
+    rc = _lib.lib().qgcm_route_chain_open_coalesced_host(ctx.handle, arena_ptr, stride, n, lens.ctypes.data, plugins,
+                                                         peer.ctypes.data,
+                                                         None if status is None else status.ctypes.data,
+                                                         out_buf.ctypes.data, out_buf.size, frames.ctypes.data,
+                                                         out.ctypes.data)
+    return _packed_result(rc, "qgcm_route_chain_open_coalesced_host", frames, out)
+
+
+def route_chain_open_gro_coalesced_host(ctx, packed, packed_len: int, bufs, stride: int, n: int, lens, plugins: int,
+                                        peer, status, out_buf, frames=None):
+    """qgcm_route_chain_open_gro_coalesced_host: route_chain_open_gro_packed_host whose delivered packets come back
+    coalesced; returns as route_chain_open_coalesced_host."""
+    import numpy as np
+
+    if frames is None:
+        frames = np.zeros(max(1, n), GSO_FRAME)
+    out = np.zeros(5, np.uint64)
+    rc = _lib.lib().qgcm_route_chain_open_gro_coalesced_host(ctx.handle, packed.ctypes.data, packed_len,
+                                                             bufs.ctypes.data, len(bufs), stride, n, lens.ctypes.data,
+                                                             plugins, peer.ctypes.data,
+                                                             None if status is None else status.ctypes.data,
+                                                             out_buf.ctypes.data, out_buf.size, frames.ctypes.data,
+                                                             out.ctypes.data)
+    return _packed_result(rc, "qgcm_route_chain_open_gro_coalesced_host", frames, out)
