@@ -1188,6 +1188,138 @@ int qgcm_route_chain_open_gro_coalesced_host(qgcm_ctx *ctx, const uint8_t *h_pac
                                              uint8_t *h_out, uint64_t out_cap, qgcm_gso_frame *h_frames,
                                              uint64_t out[5]);
 
+/* ---- DTLS 1.2 records on routed batches ---- */
+/* The record layer of quantum's `dtls` backend (socket/dtls.go, crypto/dtls.c) for established sessions: every
+ * Payload.Raw[:Length] that SSL_write would turn into one application-data record, and every record SSL_read
+ * would open, as one GPU batch.  The reference fixes the suite to ECDHE-{ECDSA,RSA}-AES256-GCM-SHA384 over DTLS
+ * 1.2 (dtls.h:19, dtls.c:194-204), so one cipher and one record format cover it.  Handshake, certificates,
+ * cookies, alerts and retransmission stay in the host's DTLS stack.
+ *
+ * Record on the wire (RFC 6347 4.1, RFC 5288 3):
+ *   type(1) = 23 | version(2) = FE FD | epoch(2) | seq(6) | length(2) = 8 + L + 16 | explicit_nonce(8) |
+ *   ciphertext(L) | tag(16)
+ * AES-256-GCM with nonce = write_IV(4) | explicit_nonce(8) and the 13 bytes of additional data
+ *   epoch(2) | seq(6) | type | version(2) | L(2, big endian).
+ * A sealed record carries explicit_nonce = epoch | seq; an opened one takes it from the record (OpenSSL's is
+ * not the sequence number).
+ *
+ * Sessions.  A session is indexed like a peer (0 .. max_keys - 1, the index the resolve launches leave in d_peer)
+ * and owns two key slots of the context, one per direction.  qgcm_dtls_sessions_set installs both keys of every
+ * session of the call in one install pass (as qgcm_set_keys) and writes the device session table (allocated on
+ * first use): slots, IVs, epochs, write_seq, and an empty anti-replay window (right edge R = 0, bitmap W = 0).
+ * Errors, nothing installed: QGCM_E_ARG (NULL context, NULL keys with count > 0, write_slot == read_slot,
+ * write_seq > 2^48, a slot named twice in the call), QGCM_E_KEY (first + count or a slot beyond max_keys).  An
+ * epoch change (a renegotiation) means qgcm_dtls_sessions_set again.  qgcm_dtls_sessions_clear marks the sessions
+ * unset and releases their key slots (qgcm_clear_keys).  qgcm_dtls_session_state reads {write_seq, R, W, set}
+ * after synchronising the context's device.  Calls that touch the same session (set, clear, seal, open, state)
+ * must be ordered by the caller: one stream, or a synchronisation between them.
+ * qgcm_dtls_key_block (host): PRF_SHA384(master_secret, "key expansion", server_random | client_random), the 72
+ * bytes client_write_key[32] | server_write_key[32] | client_write_IV[4] | server_write_IV[4] (RFC 5246 5, 6.3)
+ * from what SSL_SESSION_get_master_key, SSL_get_client_random and SSL_get_server_random return.
+ *
+ * Slot form.  The record is kept split so that it composes with the rest of the path: the slot holds
+ * ciphertext | tag at Raw[0 : L + 16] (what qgcm_chain_outgoing leaves and qgcm_deliver_pack takes is
+ * Raw[0 : Length]); the 21 bytes in front live in a side array of qgcm_dtls_hdr: b[0:13] the record header,
+ * b[13:21] the explicit nonce, b[21:32] zero after a seal and ignored by an open.  Arena 4-byte aligned, stride a
+ * multiple of 4 (as qgcm_resolve_*), the header array 16-byte aligned.
+ *
+ * d_status[i] is 1 (sealed / delivered) or 0; d_reason (may be NULL) says why, and when several apply the
+ * lowest step below wins (NO_SESSION before NOT_APPDATA / MALFORMED before AUTH before REPLAY; on the seal side
+ * NO_SESSION before MALFORMED before SEQ_EXHAUSTED).
+ *
+ * qgcm_dtls_seal, slot i with p = d_peer[i], L = d_lens[i]:
+ *   1. NO_SESSION: p >= max_keys, session unset, or its write key slot unset.
+ *   2. MALFORMED: L == 0, L > 16384 or L + 16 > stride.
+ *   3. The remaining packets of a session are numbered in arena order, seq = write_seq[p] + rank;
+ *      SEQ_EXHAUSTED when seq > 2^48 - 1.  After the call write_seq[p] has advanced by the number of packets
+ *      numbered, saturating at 2^48.
+ *   4. A sealed packet: d_hdr[i] = 23 | FE FD | write_epoch | seq48 | (8 + L + 16) | write_epoch | seq48 | zeros,
+ *      Raw[0:L] encrypted in place, tag at Raw[L : L + 16], d_lens[i] = L + 16, status 1.
+ *   A rejected packet leaves slot, header entry and length untouched.  No byte of a slot at or past L + 16 is
+ *   written.
+ * qgcm_dtls_open, slot i with p = d_peer[i], B = d_lens[i] (bytes in the slot):
+ *   1. NO_SESSION as above with the read key slot.
+ *   2. NOT_APPDATA: b[0] != 23 (handshake retransmits, alerts, change-cipher-spec: they go to the host's DTLS
+ *      stack).  Slot untouched.
+ *   3. MALFORMED: version not FE FD, epoch not read_epoch, B < 17, B > 16400, B > stride, or the length field
+ *      not 8 + B.  Slot untouched.
+ *   4. AUTH: tag mismatch.  Raw[0 : B - 16] zeroed (as qgcm_open_batch), the tag and what follows untouched.
+ *   5. REPLAY: the authentic packets of each session, in arena order, pass RFC 6347 4.1.2.6 packet by packet
+ *      (OpenSSL's bitmap rule): bit k of W means R - k was seen; s > R is accepted and the window shifts; else
+ *      rejected when R - s >= 64 or the bit is set, else accepted and the bit set.  A replayed packet keeps its
+ *      plaintext in the slot; neither d_lens[i] nor the window changes for it.  Only authentic packets count: a
+ *      forged record ahead of an authentic one with the same number does not make the latter a replay.
+ *   6. Delivered: status 1, plaintext at Raw[0 : B - 16], d_lens[i] = B - 16.
+ *   The session's (R, W) after the call is the sequential rule's end state.
+ * Both: device arrays, asynchronous on stream, work areas owned by the context (calls on one context are
+ * serialised on the device like descriptor batches); n == 0 launches nothing.  QGCM_E_ARG: NULL context or
+ * arrays (d_status included; d_reason may be NULL), arena or d_lens / d_peer not 4-byte aligned, d_hdr not 16-byte
+ * aligned, stride not a multiple of 4, below 20 or above 2^32, n > QGCM_MAX_BATCH; QGCM_E_KEY: no session was ever
+ * set on the context.  The seal's numbering launch writes a sealed record's header entry, so the GCM kernel reads
+ * header entries alike on both sides.
+ * The window and the numbering run as a stable radix sort by session (and by (session, seq) for duplicates) and
+ * reduce-then-scan launches; no workgroup waits for another and the result does not depend on scheduling.
+ *
+ * Host forms of the two ordered rules (quantum_amd/csrc/dtls_core.h), for tests and small batches; libqgcm has
+ * no host AES-GCM:
+ * qgcm_dtls_number_cpu: the seal's steps 1-3 and the header of step 4 for host arrays.  `keys` (n_sessions
+ *   entries, a NULL entry list with n_sessions == 0 allowed) describes the sessions; set[p] != 0 marks session p
+ *   usable (NULL: all); write_seq[p] is read and advanced.  hdr, lens, status and reason (may be NULL) are
+ *   written as the seal writes them; the slots are not touched.
+ * qgcm_dtls_replay_cpu: the open's step 5 over n packets given as (session, seq, authentic): accept[i] = 1 for a
+ *   delivered packet; state[2 p] = R and state[2 p + 1] = W of session p < n_sessions are read and updated; a
+ *   packet that is not authentic, or whose session is >= n_sessions, gets 0 and counts for nothing.
+ *   parallel != 0 evaluates the parallel form (prefix maximum, duplicate test, closed-form end state), 0 the
+ *   packet-by-packet rule; the two agree. */
+#define QGCM_DTLS_OK 0
+#define QGCM_DTLS_NO_SESSION 1
+#define QGCM_DTLS_NOT_APPDATA 2
+#define QGCM_DTLS_MALFORMED 3
+#define QGCM_DTLS_AUTH 4
+#define QGCM_DTLS_REPLAY 5
+#define QGCM_DTLS_SEQ_EXHAUSTED 6
+#define QGCM_DTLS_MAX_PLAIN 16384u /* RFC 6347 4.1: the longest plaintext fragment of a record */
+#define QGCM_DTLS_HDR_BYTES 21u    /* record header and explicit nonce: what travels in front of the slot's bytes */
+typedef struct qgcm_dtls_keys {
+    uint8_t write_key[32], read_key[32];
+    uint8_t write_iv[4], read_iv[4];
+    uint16_t write_epoch, read_epoch; /* 1 after a first handshake */
+    uint32_t write_slot, read_slot;   /* key slots of the context, distinct, < max_keys */
+    uint64_t write_seq;               /* next sequence number to hand out, <= 2^48 */
+} qgcm_dtls_keys;
+typedef struct qgcm_dtls_hdr {
+    uint8_t b[32];
+} qgcm_dtls_hdr;
+int qgcm_dtls_sessions_set(qgcm_ctx *ctx, uint32_t first, uint32_t count, const qgcm_dtls_keys *keys);
+int qgcm_dtls_sessions_clear(qgcm_ctx *ctx, uint32_t first, uint32_t count);
+int qgcm_dtls_session_state(qgcm_ctx *ctx, uint32_t session, uint64_t out[4]); /* {write_seq, R, W, set} */
+int qgcm_dtls_key_block(const uint8_t master[48], const uint8_t client_random[32], const uint8_t server_random[32],
+                        uint8_t out[72]);
+int qgcm_dtls_seal(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                   const uint32_t *d_peer, qgcm_dtls_hdr *d_hdr, uint8_t *d_status, uint8_t *d_reason, void *stream);
+int qgcm_dtls_open(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                   const uint32_t *d_peer, const qgcm_dtls_hdr *d_hdr, uint8_t *d_status, uint8_t *d_reason,
+                   void *stream);
+int qgcm_dtls_number_cpu(const qgcm_dtls_keys *keys, const uint8_t *set, uint64_t *write_seq, uint32_t n_sessions,
+                         uint64_t stride, uint32_t n, uint32_t *lens, const uint32_t *peer, qgcm_dtls_hdr *hdr,
+                         uint8_t *status, uint8_t *reason);
+int qgcm_dtls_replay_cpu(uint32_t n, const uint32_t *session, const uint64_t *seq, const uint8_t *authentic,
+                         uint32_t n_sessions, uint64_t *state, uint8_t *accept, int parallel);
+
+/* Split records over UDP, one record per datagram (what OpenSSL sends for application data).
+ * qgcm_udp_send_dtls: sendmmsg with two iovecs a datagram, hdr[i].b[0:21] then Raw[0 : lens[i]] of slot i, for the
+ *   slots whose status is 1 (NULL: all) and whose peer[i] < n_addrs, to addrs[peer[i]], as qgcm_udp_send_slots_to.
+ *   Returns the datagrams sent or -1.
+ * qgcm_udp_recv_dtls: recvmmsg with two iovecs: the first 21 bytes to hdr[i] (b[21:32] zeroed), the rest to slot
+ *   i, lens[i] the bytes in the slot, the sender to addrs_out[i] (may be NULL).  Waits up to timeout_ms for the
+ *   first datagram (0: no wait, < 0: for ever), then takes what is queued.  A datagram shorter than 22 bytes or
+ *   longer than 21 + stride is dropped and counted in *dropped (may be NULL).  Returns the slots filled or -1. */
+int qgcm_udp_send_dtls(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
+                       const qgcm_dtls_hdr *hdr, const uint8_t *status, const uint32_t *peer,
+                       const qgcm_peer_addr *addrs, uint32_t n_addrs);
+int qgcm_udp_recv_dtls(int fd, uint8_t *arena, uint64_t stride, uint32_t max_n, uint32_t *lens, qgcm_dtls_hdr *hdr,
+                       qgcm_peer_addr *addrs_out, int timeout_ms, uint32_t *dropped);
+
 /* ---- introspection: which kernels served this context's calls ---- */
 /* Launch counts per kernel family since qgcm_create (uniform batches launch in chunks of 2^19
  * packets; a descriptor batch launches the segmented kernel and then the per-wave kernel for its

@@ -54,6 +54,9 @@ EXPORTS = (
     "qgcm_route_chain_seal_gso_host",
     "qgcm_deliver_coalesce_work", "qgcm_deliver_coalesce", "qgcm_deliver_coalesce_cpu", "qgcm_tun_write_gso",
     "qgcm_route_chain_open_coalesced_host", "qgcm_route_chain_open_gro_coalesced_host",
+    "qgcm_dtls_sessions_set", "qgcm_dtls_sessions_clear", "qgcm_dtls_session_state", "qgcm_dtls_key_block",
+    "qgcm_dtls_seal", "qgcm_dtls_open", "qgcm_dtls_number_cpu", "qgcm_dtls_replay_cpu",
+    "qgcm_udp_send_dtls", "qgcm_udp_recv_dtls",
 )
 
 QGCM_OK = 0
@@ -156,6 +159,14 @@ class GsoFrame(C.Structure):
     _fields_ = [("off", C.c_uint32), ("len", C.c_uint32), ("first", C.c_uint32), ("count", C.c_uint32),
                 ("gso_size", C.c_uint16), ("hdr_len", C.c_uint16), ("l4_off", C.c_uint16), ("csum_off", C.c_uint16),
                 ("kind", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DtlsKeys(C.Structure):
+    """qgcm_dtls_keys: one session's two keys, IVs, epochs, key slots and next sequence number -- 96 bytes."""
+
+    _fields_ = [("write_key", C.c_uint8 * 32), ("read_key", C.c_uint8 * 32), ("write_iv", C.c_uint8 * 4),
+                ("read_iv", C.c_uint8 * 4), ("write_epoch", C.c_uint16), ("read_epoch", C.c_uint16),
+                ("write_slot", C.c_uint32), ("read_slot", C.c_uint32), ("write_seq", C.c_uint64)]
 
 
 _lib: C.CDLL | None = None
@@ -328,6 +339,17 @@ def _bind(L: C.CDLL) -> None:
         L.qgcm_tun_write_gso.argtypes = [C.c_int, vp, u64, vp, u32, vp]
         L.qgcm_route_chain_open_coalesced_host.argtypes = [vp, vp, u64, u32, vp, u32, vp, vp, vp, u64, vp, vp]
         L.qgcm_route_chain_open_gro_coalesced_host.argtypes = [vp, vp, u64, vp, u32, u64, u32, vp, u32, vp, vp, vp, u64, vp, vp]
+    if hasattr(L, "qgcm_dtls_seal"):  # (older builds loaded by the A/B tools lack the DTLS record layer)
+        L.qgcm_dtls_sessions_set.argtypes = [vp, u32, u32, vp]
+        L.qgcm_dtls_sessions_clear.argtypes = [vp, u32, u32]
+        L.qgcm_dtls_session_state.argtypes = [vp, u32, vp]
+        L.qgcm_dtls_key_block.argtypes = [u8p, u8p, u8p, vp]
+        L.qgcm_dtls_seal.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, vp, vp]
+        L.qgcm_dtls_open.argtypes = [vp, vp, u64, u32, vp, vp, vp, vp, vp, vp]
+        L.qgcm_dtls_number_cpu.argtypes = [vp, vp, vp, u32, u64, u32, vp, vp, vp, vp, vp]
+        L.qgcm_dtls_replay_cpu.argtypes = [u32, vp, vp, vp, u32, vp, vp, i32]
+        L.qgcm_udp_send_dtls.argtypes = [C.c_int, vp, u64, u32, vp, vp, vp, vp, vp, u32]
+        L.qgcm_udp_recv_dtls.argtypes = [C.c_int, vp, u64, u32, vp, vp, vp, C.c_int, vp]
     if hasattr(L, "qgcm_tun_open"):  # (older builds loaded by the A/B tools lack the TUN calls)
         L.qgcm_tun_open.argtypes = [C.c_char_p, C.c_int, vp, C.c_char_p, sz]
         L.qgcm_tun_up.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]

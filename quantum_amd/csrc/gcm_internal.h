@@ -471,6 +471,36 @@ struct GsoArgs {
     uint32_t net, mask, gateway, own_ip;
 };
 hipError_t launch_gso_resolve(const GsoArgs &a, hipStream_t s);
+// DTLS 1.2 records on routed batches (dtls_kernels.hip, gcm_dtls_kernel in gcm_kernels.hip, dtls_core.h;
+// include/qgcm.h "DTLS 1.2 records on routed batches").  One call's arrays; `work` is dtls_work_bytes(n, max_keys)
+// bytes, 256-B aligned, and starts with the call's n descriptors (dtls_work_descs), which the launches below
+// write and the GCM launch between them reads through launch_quad_worklist.
+struct DtlsSession;
+struct DtlsCall {
+    uint64_t stride;
+    uint32_t n, max_keys;
+    uint32_t *lens;
+    const uint32_t *peer;
+    qgcm_dtls_hdr *hdr;         // written by the seal only
+    uint8_t *status, *reason;   // reason may be NULL
+    DtlsSession *sessions;      // [max_keys]
+    const uint8_t *key_valid;   // [max_keys]
+    qgcm_desc *descs;           // set by the launches (the head of work)
+    void *work;
+    uint64_t work_bytes;
+};
+uint64_t dtls_work_bytes(uint32_t n, uint32_t max_keys);
+qgcm_desc *dtls_work_descs(const DtlsCall &c);
+// seal: checks, sequence numbers in arena order, header entries, lengths, seal descriptors, write_seq advanced
+hipError_t launch_dtls_seal_number(const DtlsCall &c, hipStream_t s);
+// open, before the GCM launch: checks and open descriptors; after it: AUTH, the replay window, statuses, lengths
+hipError_t launch_dtls_open_prep(const DtlsCall &c, hipStream_t s);
+hipError_t launch_dtls_open_replay(const DtlsCall &c, hipStream_t s);
+// gcm_dtls_kernel over a worklist built from the call's descriptors (b as for the per-wave descriptor kernel;
+// b.status is written for every packet of the worklist)
+int dtls_waves();
+hipError_t launch_dtls_packets(bool seal, const Batch &b, const uint32_t *d_peer, const DtlsSession *sessions,
+                               const qgcm_dtls_hdr *hdr, int grid, hipStream_t s);
 // qgcm_send_plan_host plans on the device from this many packets on (QGCM_PLAN_DEVICE_MIN at qgcm_create): the
 // measured crossover -- 181 against 186 us at 65536, 319 against 993 us at 262144
 constexpr uint32_t kPlanDeviceMin = 65536;

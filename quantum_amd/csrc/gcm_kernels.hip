@@ -24,6 +24,7 @@
 
 #include <algorithm>
 
+#include "dtls_core.h"
 #include "gcm_internal.h"
 
 namespace qgcm {
@@ -964,6 +965,267 @@ extern "C" int qgcm_debug_quad_stats(unsigned long long *out, int n, int reset) 
     return 0;
 }
 #endif
+
+// ---------------------------------------------------------------------------------------------
+// DTLS 1.2 records (include/qgcm.h "DTLS 1.2 records on routed batches"): gcm_dtls_kernel, the per-wave
+// descriptor kernel (gcm_quad_kernel<kSeal, true>: engine Tab2, each wave's 4-bit comb of its key's H^4 in its
+// own 8 KiB of LDS, key-sorted 16-packet tiles from launch_quad_worklist handed out by the global tile
+// counter) over another frame.  dtls_packet is quad_packet's sibling: the record starts at Raw[0]; the nonce is
+// the session's IV and the explicit nonce of the packet's header entry (b[13:21]); lane 3 starts its Horner
+// chain with the 13 bytes epoch | seq | type | version | L built from the header entry, zero-padded to a block;
+// the length block counts 13 bytes of additional data; the tag is written or compared at Raw[L:] with nothing
+// behind it.  The header entry is complete before the launch (the numbering kernel of dtls_kernels.hip writes a
+// sealed record's with the sequence number it hands out), so seal and open read it alike.
+
+// The 16-byte tag at byte L of data (any alignment; data 4-aligned), as read_tag, but no byte at or past
+// L + 16 is read: the fifth dword only when L % 4 != 0, where it holds a byte of the tag and ends inside
+// the slot (the stride is a multiple of 4).
+__device__ __forceinline__ void dtls_read_tag(const uint8_t *data, uint32_t L, uint32_t &g0, uint32_t &g1, uint32_t &g2,
+                                              uint32_t &g3) {
+    const uint32_t s = L & 3u;
+    const uint32_t *t = reinterpret_cast<const uint32_t *>(data + (L & ~3u));
+    const uint32_t w0 = t[0], w1 = t[1], w2 = t[2], w3 = t[3];
+    const uint32_t w4 = s ? load_bytes(data + (L & ~3u) + 16, s) : 0u;
+    g0 = __builtin_amdgcn_alignbyte(w1, w0, s);
+    g1 = __builtin_amdgcn_alignbyte(w2, w1, s);
+    g2 = __builtin_amdgcn_alignbyte(w3, w2, s);
+    g3 = __builtin_amdgcn_alignbyte(w4, w3, s);
+}
+// Writes prefix (s = L % 4 bytes, the end of the ciphertext) and the tag at data + (L & ~3): 4 dwords + s
+// bytes, never touching a byte at or past L + 16 (write_tail without the nonce).
+__device__ __forceinline__ void dtls_write_tag(uint8_t *data, uint32_t L, uint32_t g0, uint32_t g1, uint32_t g2,
+                                               uint32_t g3, uint32_t prefix) {
+    const uint32_t s = L & 3u;
+    uint32_t *t = reinterpret_cast<uint32_t *>(data + (L & ~3u));
+    const uint32_t sh = 32 - 8 * s;  // 32 when s == 0
+    t[0] = (uint32_t)((((uint64_t)g0 << 32) | ((uint64_t)prefix << sh)) >> sh);
+    t[1] = funnel(g1, g0, sh);
+    t[2] = funnel(g2, g1, sh);
+    t[3] = funnel(g3, g2, sh);
+    if (s) store_bytes(data + (L & ~3u) + 16, g3 >> sh, s);
+}
+
+// One record of a quad tile (4 lanes, lane m owns blocks b = m mod 4): CTR + GHASH + tag, in place.
+// iv: the session's write (seal) or read (open) IV; hb: the packet's header entry (16-B aligned).
+template <bool kSeal, class Eng>
+__device__ __forceinline__ void dtls_packet(const Batch &b, const Eng &eng, uint32_t pkt, uint64_t off, uint32_t L,
+                                            uint32_t wkey, uint32_t m, uint32_t gH4, uint32_t iv,
+                                            const qgcm_dtls_hdr *hb) {
+    const uint4 *Hg = b.gh_table + (size_t)wkey * kGhEntries;  // comb tables of H^k (global)
+    uint8_t *data = b.arena + off;
+
+    const uint32_t *hw = reinterpret_cast<const uint32_t *>(hb);
+    const uint32_t h3 = hw[3], h4 = hw[4], h5 = hw[5];
+    const uint32_t n0 = iv;
+    const uint32_t n1 = __builtin_amdgcn_alignbyte(h4, h3, 1);  // b[13:17]
+    const uint32_t n2 = __builtin_amdgcn_alignbyte(h5, h4, 1);  // b[17:21]
+    const uint32_t nfull = L >> 4, r = L & 15u;
+    const uint32_t d = nfull + (r ? 1u : 0u);  // data blocks incl. the partial one
+
+    // lane 3 starts its chain with the additional data block (block -1):
+    // epoch(2) | seq(6) = b[3:11], type | version = b[0:3], L big endian, three zero bytes
+    uint32_t z0 = 0, z1 = 0, z2 = 0, z3 = 0;
+    if (m == 3) {
+        const uint32_t h0 = hw[0], h1 = hw[1], h2 = hw[2];
+        z0 = __builtin_amdgcn_alignbyte(h1, h0, 3);
+        z1 = __builtin_amdgcn_alignbyte(h2, h1, 3);
+        z2 = (h0 & 0x00ffffffu) | ((L >> 8) << 24);
+        z3 = L & 0xffu;
+    }
+    int blast = -1;
+
+    uint32_t e0 = 0, e1 = 0, e2 = 0, e3 = 0;  // E_K(J0)
+    uint32_t prefix = 0;
+    {
+    Ctr cc;
+    uint32_t hi = 0;
+    eng.setup(cc, n0, n1, n2, 0);
+    for (uint32_t bi = m; bi < nfull; bi += 4) {
+        const uint32_t ctr = bi + 2;  // inc32(J0) + bi
+        if ((ctr >> 8) != hi) {
+            hi = ctr >> 8;
+            eng.setup(cc, n0, n1, n2, hi);
+        }
+        // the data load is issued before the AES rounds so its latency hides behind them
+        W4 *p = reinterpret_cast<W4 *>(data + 16u * bi);
+        const W4 in = load_block(p);
+        uint32_t k0, k1, k2, k3;
+        eng.block(cc, ctr & 0xffu, k0, k1, k2, k3);
+        const W4 out = {in.x ^ k0, in.y ^ k1, in.z ^ k2, in.w ^ k3};
+        store_block(p, out);
+        const W4 &c = kSeal ? out : in;
+        eng.ghash(z0, z1, z2, z3, gH4);
+        z0 ^= c.x;
+        z1 ^= c.y;
+        z2 ^= c.z;
+        z3 ^= c.w;
+        blast = (int)bi;
+    }
+    // One more slot: the partial last block (lane nfull % 4) and E_K(J0) (lane d % 4, the lane
+    // with the fewest data blocks) share one AES pass.
+    const bool part = r && (nfull & 3u) == m;
+    if (part || m == (d & 3u)) {
+        const uint32_t ctr = part ? nfull + 2 : 1u;  // inc32(J0) + nfull, or J0
+        if ((ctr >> 8) != hi) {
+            hi = ctr >> 8;
+            eng.setup(cc, n0, n1, n2, hi);
+        }
+        uint32_t k0, k1, k2, k3;
+        eng.block(cc, ctr & 0xffu, k0, k1, k2, k3);
+        if (part) {
+            uint8_t *blk = data + 16u * nfull;
+            // reads into the tag area (seal: the 16 bytes the tag will take): below L + 16, inside the slot
+            const W4 in = *reinterpret_cast<const W4 *>(blk);
+            const uint32_t q = r >> 2, sb = r & 3u;
+            const uint32_t o0 = in.x ^ k0, o1 = in.y ^ k1, o2 = in.z ^ k2, o3 = in.w ^ k3;
+            uint32_t *bw = reinterpret_cast<uint32_t *>(blk);
+            if (q > 0) bw[0] = o0;
+            if (q > 1) bw[1] = o1;
+            if (q > 2) bw[2] = o2;
+            const uint32_t oq = sel4(q, o0, o1, o2, o3) & lowmask(sb);
+            W4 c = kSeal ? W4{o0, o1, o2, o3} : in;
+            if (kSeal)
+                prefix = oq;  // written with the tag by dtls_write_tag
+            else
+                store_bytes(blk + 4 * q, oq, sb);
+            c.x &= q > 0 ? 0xffffffffu : lowmask(sb);
+            c.y &= q > 1 ? 0xffffffffu : (q == 1 ? lowmask(sb) : 0u);
+            c.z &= q > 2 ? 0xffffffffu : (q == 2 ? lowmask(sb) : 0u);
+            c.w &= q == 3 ? lowmask(sb) : 0u;
+            eng.ghash(z0, z1, z2, z3, gH4);
+            z0 ^= c.x;
+            z1 ^= c.y;
+            z2 ^= c.z;
+            z3 ^= c.w;
+            blast = (int)nfull;
+        } else {
+            e0 = k0;
+            e1 = k1;
+            e2 = k2;
+            e3 = k3;
+        }
+    }
+    }
+    // Y = sum_m Z_m * H^(e_m)  ^  ([len(A)]||[len(C)]) * H,  e_m = d + 1 - b_last(m) in [2, 5]
+    {
+        const uint32_t em = d + 1u - (uint32_t)blast;
+        const uint32_t tsel = em == 2 ? kGhH2 : em == 3 ? kGhH3 : em == 4 ? kGhH4 : kGhH5;
+        ghash_mul_global(z0, z1, z2, z3, Hg + tsel);
+        uint32_t l0, l1, l2, l3;
+        ghash_lenblock_global(13u, L, Hg, l0, l1, l2, l3);
+        z0 = quad_xor(z0) ^ l0;
+        z1 = quad_xor(z1) ^ l1;
+        z2 = quad_xor(z2) ^ l2;
+        z3 = quad_xor(z3) ^ l3;
+    }
+    e0 = quad_xor(e0);
+    e1 = quad_xor(e1);
+    e2 = quad_xor(e2);
+    e3 = quad_xor(e3);
+    const uint32_t t0 = z0 ^ e0, t1 = z1 ^ e1, t2 = z2 ^ e2, t3 = z3 ^ e3;
+    // the lane owning the partial block (or lane 0) writes the tag
+    const uint32_t owner = r ? (nfull & 3u) : 0u;
+    if (kSeal) {
+        if (m == owner) {
+            dtls_write_tag(data, L, t0, t1, t2, t3, prefix);
+            b.status[pkt] = 1;
+        }
+    } else {
+        uint32_t g0, g1, g2, g3;
+        dtls_read_tag(data, L, g0, g1, g2, g3);  // the tag is never written by Open
+        const bool ok = ((t0 ^ g0) | (t1 ^ g1) | (t2 ^ g2) | (t3 ^ g3)) == 0;
+        if (!ok) {
+            // as qgcm_open_batch: zero the would-be plaintext on a tag mismatch
+            for (uint32_t bi = m; bi < nfull; bi += 4) {
+                const W4 zz = {0, 0, 0, 0};
+                *reinterpret_cast<W4 *>(data + 16u * bi) = zz;
+            }
+            if (r && m == owner) {
+                uint32_t *bw = reinterpret_cast<uint32_t *>(data + 16u * nfull);
+                for (uint32_t w = 0; w < (r >> 2); ++w) bw[w] = 0;
+                store_bytes(data + 16u * nfull + (r & ~3u), 0, r & 3u);
+            }
+        }
+        if (m == 0) b.status[pkt] = ok ? 1 : 0;
+    }
+}
+
+// What the DTLS launch reads beside the Batch: the packets' sessions (checked by the launch that wrote the
+// descriptors), the session table and the header entries.
+struct DtlsArgs {
+    const uint32_t *peer;
+    const DtlsSession *sessions;
+    const qgcm_dtls_hdr *hdr;
+};
+
+constexpr uint32_t kDtlsLds = kTeBytes + (uint32_t)quad_waves<true>() * kGhBytes;  // Te, then a comb per wave
+
+template <bool kSeal>
+__global__ void __launch_bounds__(quad_waves<true>() * 64) __attribute__((amdgpu_waves_per_eu(quad_wpe<true>(),
+                                                                                               quad_wpe<true>())))
+gcm_dtls_kernel(Batch b, const uint32_t *__restrict__ rk_table, DtlsArgs a) {
+    constexpr uint32_t kW = quad_waves<true>();
+    constexpr uint32_t kT = kW * 64;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint32_t m = lane & 3u;   // block residue owned by this lane
+    const uint32_t qd = lane >> 2;  // packet slot within the wave tile (16 per wave)
+
+    // dword i of the 64 KiB of T-tables: row x = i/64, slot i%64 (< 32: Te0, else Te1)
+    for (uint32_t i = threadIdx.x; i < kTeBytes / 4; i += kT) {
+        const uint32_t x = i >> 6, slot = i & 63u;
+        lds_st32(4 * i, b.te[(slot >> 5) * 256u + x]);
+    }
+    __syncthreads();
+
+    const uint32_t lb = (lane & 31u) << 2;
+    const uint32_t m8 = vreg(0x0000ff00u);
+    const uint32_t gH4 = kTeBytes + wave * kGhBytes;  // this wave's H^4 table, reloaded when its key changes
+    uint32_t cur_key = 0xffffffffu;
+    const uint32_t ntiles = b.n_items >> 4;
+
+    uint32_t tile;
+    {
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(b.tile_counter, 1u);
+        tile = __builtin_amdgcn_readfirstlane(__shfl(t, 0));
+    }
+    for (; tile < ntiles;) {
+        const uint32_t pkt = b.worklist[tile * 16u + qd];
+        const bool valid = pkt != 0xffffffffu;
+        qgcm_desc dsc = {0, 0, 0};
+        if (valid) dsc = b.descs[pkt];
+        const uint64_t off = dsc.offset;
+        uint32_t L = kSeal ? dsc.len : dsc.len - QGCM_OVERHEAD;  // open descriptors carry B - 16 + 28
+        uint32_t wkey = cur_key;
+        const uint64_t vmask = __ballot(valid);
+        if (vmask != 0) {
+            wkey = __builtin_amdgcn_readfirstlane(__shfl(dsc.key_idx, __ffsll((unsigned long long)vmask) - 1));
+            if (wkey != cur_key) {
+                const uint4 *src = b.gh_table + (size_t)wkey * kGhEntries + kGhH4;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    const uint32_t e = r * 64 + lane;
+                    lds_st_comb(gH4, e, src[e]);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                cur_key = wkey;
+            }
+        }
+        // next tile (wave-uniform), fetched before this one's work
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(b.tile_counter, 1u);
+        tile = __builtin_amdgcn_readfirstlane(__shfl(t, 0));
+        asm volatile("" : "+v"(L));
+        if (!valid) continue;
+        const DtlsSession *ss = a.sessions + a.peer[pkt];
+        const uint32_t iv = kSeal ? ss->write_iv : ss->read_iv;
+        const Keys kk = {rk_table + (size_t)wkey * kRkWords, rk_table + (size_t)wkey * kRkWords + 64};
+        dtls_packet<kSeal>(b, Tab2{kk, {lb, m8}}, pkt, off, L, wkey, m, gH4, iv, a.hdr + pkt);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // Descriptor batches through the Tab2F engine (BASELINE config 3: any key mix, any lengths):
@@ -2176,6 +2438,15 @@ hipError_t init_kernels() {
                                 k == reinterpret_cast<const void *>(&gcm_resident_kernel) ? kResLds : kOneLds);
         if (e != hipSuccess) return e;
     }
+    for (const void *k : {reinterpret_cast<const void *>(&gcm_dtls_kernel<true>),
+                          reinterpret_cast<const void *>(&gcm_dtls_kernel<false>)}) {
+        hipFuncAttributes a;
+        hipError_t e = hipFuncGetAttributes(&a, k);
+        if (e != hipSuccess) return e;
+        if (a.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kDtlsLds);
+        if (e != hipSuccess) return e;
+    }
     for (NonceDest d : {kNonceArray, kNonceUniform, kNonceDescs}) {  // T-tables at LDS 0, as above
         const void *k = nonce_kernel_of(d);
         hipFuncAttributes a;
@@ -2200,6 +2471,17 @@ hipError_t launch_packets(bool seal, int variant, const Batch &b, int grid, hipS
     const Variant &v = g_variants[variant_slot(variant)];
     void *args[] = {const_cast<Batch *>(&b), const_cast<uint32_t **>(&b.rk_table)};
     return hipLaunchKernel(seal ? v.seal : v.open, dim3(grid), dim3(v.waves * 64), args, v.lds, s);
+}
+
+int dtls_waves() { return quad_waves<true>(); }
+
+hipError_t launch_dtls_packets(bool seal, const Batch &b, const uint32_t *d_peer, const DtlsSession *sessions,
+                               const qgcm_dtls_hdr *hdr, int grid, hipStream_t s) {
+    DtlsArgs a{d_peer, sessions, hdr};
+    void *args[] = {const_cast<Batch *>(&b), const_cast<uint32_t **>(&b.rk_table), &a};
+    const void *k = seal ? reinterpret_cast<const void *>(&gcm_dtls_kernel<true>)
+                         : reinterpret_cast<const void *>(&gcm_dtls_kernel<false>);
+    return hipLaunchKernel(k, dim3(grid), dim3(quad_waves<true>() * 64), args, kDtlsLds, s);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -300,6 +300,58 @@ int qgcm_derive_keys(const uint8_t *secrets, const uint8_t *salts, uint32_t coun
     return QGCM_OK;
 }
 
+// The DTLS 1.2 key block of the reference's suites (ECDHE-*-AES256-GCM-SHA384; include/qgcm.h "DTLS 1.2 records
+// on routed batches"): P_SHA384(master, "key expansion" | server_random | client_random), RFC 5246 5 and 6.3.
+// SHA-384 is SHA-512's compression function from another initial value (FIPS 180-4 5.3.4), truncated to 48 bytes.
+int qgcm_dtls_key_block(const uint8_t master[48], const uint8_t client_random[32], const uint8_t server_random[32],
+                        uint8_t out[72]) {
+    if (!master || !client_random || !server_random || !out) return QGCM_E_ARG;
+    static const uint64_t kSha384H0[8] = {
+        0xcbbb9d5dc1059ed8ULL, 0x629a292a367cd507ULL, 0x9159015a3070dd17ULL, 0x152fecd8f70e5939ULL,
+        0x67332667ffc00b31ULL, 0x8eb44a8768581511ULL, 0xdb0c2e0d64f98fa7ULL, 0x47b5481dbefa4fa4ULL,
+    };
+    auto sha384 = [&]() {
+        Sha512 s;
+        memcpy(s.h, kSha384H0, sizeof s.h);
+        return s;
+    };
+    // HMAC-SHA384 (RFC 2104; block 128 B, key 48 B) from the two padded-key states
+    uint8_t ip[128], op[128];
+    for (int i = 0; i < 128; ++i) {
+        const uint8_t k = i < 48 ? master[i] : 0;
+        ip[i] = k ^ 0x36;
+        op[i] = k ^ 0x5c;
+    }
+    auto hmac = [&](const uint8_t *a, size_t an, const uint8_t *b, size_t bn, uint8_t mac[48]) {
+        uint8_t t[64], o[64];
+        Sha512 in = sha384(), ou = sha384();
+        in.update(ip, 128);
+        in.update(a, an);
+        if (bn) in.update(b, bn);
+        in.final(t);
+        ou.update(op, 128);
+        ou.update(t, 48);
+        ou.final(o);
+        memcpy(mac, o, 48);
+    };
+    uint8_t seed[13 + 64];
+    memcpy(seed, "key expansion", 13);
+    memcpy(seed + 13, server_random, 32);
+    memcpy(seed + 45, client_random, 32);
+    uint8_t a[48], blk[48];
+    hmac(seed, sizeof seed, nullptr, 0, a);  // A(1)
+    for (size_t done = 0; done < 72; done += 48) {
+        hmac(a, 48, seed, sizeof seed, blk);
+        memcpy(out + done, blk, 72 - done < 48 ? 72 - done : 48);
+        hmac(a, 48, nullptr, 0, a);  // A(i + 1)
+    }
+    explicit_bzero(ip, sizeof ip);
+    explicit_bzero(op, sizeof op);
+    explicit_bzero(blk, sizeof blk);
+    explicit_bzero(a, sizeof a);
+    return QGCM_OK;
+}
+
 int qgcm_x25519_base(uint8_t pub[32], const uint8_t priv[32]) {
     if (!pub || !priv) return QGCM_E_ARG;
     uint8_t nine[32] = {9};

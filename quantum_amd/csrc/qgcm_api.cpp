@@ -23,6 +23,7 @@
 
 #include "../../include/qgcm.h"
 #include "chain_claim.h"
+#include "dtls_core.h"
 #include "gcm_internal.h"
 #include "kdf_core.h"
 
@@ -176,6 +177,16 @@ struct qgcm_ctx {
 
     // the route table, link counters and host-pipeline staging of the qgcm_route* calls (route.cpp)
     qgcm::RouteState *route = nullptr;
+
+    // DTLS sessions (include/qgcm.h "DTLS 1.2 records on routed batches"): the device table, made by the first
+    // qgcm_dtls_sessions_set; the host's view of which sessions are set and of their key slots (dtls_mu); the
+    // work area of qgcm_dtls_seal / qgcm_dtls_open (ws_mu, as d_qws)
+    qgcm::DtlsSession *d_dtls = nullptr;
+    std::vector<uint8_t> dtls_set;
+    std::vector<uint32_t> dtls_slots;  // write and read slot of session p at [2 p], [2 p + 1]
+    std::mutex dtls_mu;
+    void *d_dtls_work = nullptr;
+    size_t dtls_work_cap = 0;
 };
 
 namespace {
@@ -1000,6 +1011,8 @@ void qgcm_destroy(qgcm_ctx *ctx) {
     hipFree(ctx->d_sbox);
     hipFree(ctx->d_key_valid);
     hipFree(ctx->d_qws);
+    hipFree(ctx->d_dtls);
+    hipFree(ctx->d_dtls_work);
     route_state_destroy(ctx->route);
     auto free_slot = [](qgcm_ctx::OneSlot &sl) {
         if (sl.h) hipHostFree(sl.h);
@@ -1972,6 +1985,204 @@ int qgcm_stream_copy(qgcm_ctx *ctx, void *d_dst, const void *d_src, uint64_t byt
         return QGCM_E_ARG;
     if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
     return hip_fail(launch_stream_copy(d_dst, d_src, bytes, ctx->num_cus, (hipStream_t)stream));
+}
+
+}  // extern "C"
+
+// ---- DTLS 1.2 records on routed batches (include/qgcm.h; dtls_kernels.hip, gcm_dtls_kernel, dtls_core.h) ----
+namespace {
+
+uint32_t iv_word(const uint8_t iv[4]) {
+    return (uint32_t)iv[0] | ((uint32_t)iv[1] << 8) | ((uint32_t)iv[2] << 16) | ((uint32_t)iv[3] << 24);
+}
+
+// seal: numbering, worklist, gcm_dtls_kernel<true>; open: checks, worklist, gcm_dtls_kernel<false>, the window
+int dtls_run(qgcm_ctx *ctx, bool seal, uint8_t *arena, uint64_t stride, uint32_t n, uint32_t *lens, const uint32_t *peer,
+             qgcm_dtls_hdr *hdr, uint8_t *status, uint8_t *reason, hipStream_t s) {
+    if (!ctx || n > QGCM_MAX_BATCH || (stride & 3) || stride < 20 || stride > (1ull << 32)) return QGCM_E_ARG;
+    if (n && (!arena || !lens || !peer || !hdr || !status)) return QGCM_E_ARG;
+    if (((uintptr_t)arena & 3) || ((uintptr_t)lens & 3) || ((uintptr_t)peer & 3) || ((uintptr_t)hdr & 15)) return QGCM_E_ARG;
+    if (n == 0) return QGCM_OK;
+    if (!ctx->d_dtls) return QGCM_E_KEY;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    // the work areas are reused by the next call on any stream: serialised per context, on the host and on the
+    // device, as the descriptor batches are (run_descs)
+    std::lock_guard<std::mutex> g(ctx->ws_mu);
+    if (ctx->ws_pending && hipStreamWaitEvent(s, ctx->ws_done, 0) != hipSuccess) return QGCM_E_HIP;
+    const uint64_t need = dtls_work_bytes(n, ctx->max_keys);
+    if (need > ctx->dtls_work_cap) {
+        if (ctx->d_dtls_work && (hipDeviceSynchronize() != hipSuccess || hipFree(ctx->d_dtls_work) != hipSuccess))
+            return QGCM_E_HIP;
+        ctx->d_dtls_work = nullptr;
+        ctx->dtls_work_cap = 0;
+        if (hipMalloc(&ctx->d_dtls_work, need) != hipSuccess) return QGCM_E_NOMEM;
+        ctx->dtls_work_cap = need;
+    }
+    uint32_t items = 0;
+    const size_t qneed = quad_worklist_bytes(n, ctx->max_keys, &items);
+    if (qneed > ctx->qws_cap) {
+        if (ctx->d_qws) hipFree(ctx->d_qws);
+        ctx->d_qws = nullptr;
+        ctx->qws_cap = 0;
+        if (hipMalloc(&ctx->d_qws, qneed) != hipSuccess) return QGCM_E_NOMEM;
+        ctx->qws_cap = qneed;
+    }
+    DtlsCall c{};
+    c.stride = stride;
+    c.n = n;
+    c.max_keys = ctx->max_keys;
+    c.lens = lens;
+    c.peer = peer;
+    c.hdr = hdr;
+    c.status = status;
+    c.reason = reason;
+    c.sessions = ctx->d_dtls;
+    c.key_valid = ctx->d_key_valid;
+    c.work = ctx->d_dtls_work;
+    c.work_bytes = ctx->dtls_work_cap;
+    if ((seal ? launch_dtls_seal_number(c, s) : launch_dtls_open_prep(c, s)) != hipSuccess) return QGCM_E_HIP;
+    Batch b = base_batch(ctx);
+    b.arena = arena;
+    b.descs = dtls_work_descs(c);
+    b.status = status;
+    b.n = n;
+    QuadWorklist q{};
+    // (no status array: the launches above have written every packet's)
+    if (launch_quad_worklist(b.descs, n, ctx->max_keys, ctx->d_key_valid, seal, ctx->d_qws, ctx->qws_cap, &q, s, nullptr,
+                             small_worklist(n, ctx->small_wl)) != hipSuccess)
+        return QGCM_E_HIP;
+    b.worklist = q.worklist;
+    b.tile_keys = q.tile_keys;
+    b.tile_counter = q.tile_counter;
+    b.n_items = q.n_items;
+    const uint32_t tiles = (b.n_items + 15) / 16, waves = (uint32_t)dtls_waves();
+    const uint32_t cus = (uint32_t)std::max(1, ctx->num_cus - resident_workers_running(ctx->res.load(std::memory_order_acquire)));
+    const uint32_t wgs = std::max(1u, (tiles + waves - 1) / waves);
+    if (launch_dtls_packets(seal, b, peer, ctx->d_dtls, hdr, (int)std::min(wgs, cus), s) != hipSuccess) return QGCM_E_HIP;
+    if (!seal && launch_dtls_open_replay(c, s) != hipSuccess) return QGCM_E_HIP;
+    if (hipEventRecord(ctx->ws_done, s) != hipSuccess) return QGCM_E_HIP;
+    ctx->ws_pending = true;
+    return QGCM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qgcm_dtls_sessions_set(qgcm_ctx *ctx, uint32_t first, uint32_t count, const qgcm_dtls_keys *keys) {
+    if (!ctx || (count && !keys)) return QGCM_E_ARG;
+    if ((uint64_t)first + count > ctx->max_keys) return QGCM_E_KEY;
+    std::vector<uint32_t> slots;
+    for (uint32_t j = 0; j < count; ++j) {
+        const qgcm_dtls_keys &k = keys[j];
+        if (k.write_slot == k.read_slot || k.write_seq > kDtlsSeqEnd) return QGCM_E_ARG;
+        if (k.write_slot >= ctx->max_keys || k.read_slot >= ctx->max_keys) return QGCM_E_KEY;
+        slots.push_back(k.write_slot);
+        slots.push_back(k.read_slot);
+    }
+    std::sort(slots.begin(), slots.end());
+    if (std::adjacent_find(slots.begin(), slots.end()) != slots.end()) return QGCM_E_ARG;
+    if (count == 0) return QGCM_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    std::lock_guard<std::mutex> lk(ctx->dtls_mu);
+    if (!ctx->d_dtls) {
+        DtlsSession *t = nullptr;
+        const size_t bytes = (size_t)ctx->max_keys * sizeof(DtlsSession);
+        if (hipMalloc(&t, bytes) != hipSuccess) return QGCM_E_NOMEM;
+        if (hipMemset(t, 0, bytes) != hipSuccess) {
+            hipFree(t);
+            return QGCM_E_HIP;
+        }
+        ctx->dtls_set.assign(ctx->max_keys, 0);
+        ctx->dtls_slots.assign(2ull * ctx->max_keys, 0);
+        ctx->d_dtls = t;
+    }
+    // both keys of every session in one install pass
+    std::vector<uint8_t> h_keys(64ull * count);
+    std::vector<KeyRun> runs(2ull * count);
+    std::vector<DtlsSession> tab(count);
+    for (uint32_t j = 0; j < count; ++j) {
+        const qgcm_dtls_keys &k = keys[j];
+        memcpy(&h_keys[64ull * j], k.write_key, 32);
+        memcpy(&h_keys[64ull * j + 32], k.read_key, 32);
+        runs[2 * j] = KeyRun{k.write_slot, 1, 2 * j};
+        runs[2 * j + 1] = KeyRun{k.read_slot, 1, 2 * j + 1};
+        DtlsSession &t = tab[j];
+        t = DtlsSession{};
+        t.write_slot = k.write_slot;
+        t.read_slot = k.read_slot;
+        t.write_iv = iv_word(k.write_iv);
+        t.read_iv = iv_word(k.read_iv);
+        t.write_epoch = k.write_epoch;
+        t.read_epoch = k.read_epoch;
+        t.set = 1;
+        t.write_seq = k.write_seq;
+    }
+    uint8_t *d_keys = nullptr;
+    if (hipMalloc(&d_keys, h_keys.size()) != hipSuccess) {
+        explicit_bzero(h_keys.data(), h_keys.size());
+        return QGCM_E_NOMEM;
+    }
+    int rc = install_device_keys(ctx, runs.data(), runs.size(), d_keys, 2 * count, h_keys.data());
+    hipFree(d_keys);
+    explicit_bzero(h_keys.data(), h_keys.size());
+    if (rc != QGCM_OK) return rc;
+    if (hipMemcpy(ctx->d_dtls + first, tab.data(), tab.size() * sizeof(DtlsSession), hipMemcpyHostToDevice) != hipSuccess)
+        return QGCM_E_HIP;
+    for (uint32_t j = 0; j < count; ++j) {
+        ctx->dtls_set[first + j] = 1;
+        ctx->dtls_slots[2ull * (first + j)] = keys[j].write_slot;
+        ctx->dtls_slots[2ull * (first + j) + 1] = keys[j].read_slot;
+    }
+    return QGCM_OK;
+}
+
+int qgcm_dtls_sessions_clear(qgcm_ctx *ctx, uint32_t first, uint32_t count) {
+    if (!ctx) return QGCM_E_ARG;
+    if ((uint64_t)first + count > ctx->max_keys) return QGCM_E_KEY;
+    if (count == 0) return QGCM_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    std::lock_guard<std::mutex> lk(ctx->dtls_mu);
+    if (!ctx->d_dtls) return QGCM_OK;  // nothing was ever set
+    if (hipMemset(ctx->d_dtls + first, 0, (size_t)count * sizeof(DtlsSession)) != hipSuccess) return QGCM_E_HIP;
+    int rc = QGCM_OK;
+    for (uint32_t p = first; p < first + count; ++p) {
+        if (!ctx->dtls_set[p]) continue;
+        ctx->dtls_set[p] = 0;
+        for (int d = 0; d < 2; ++d) {
+            const int r = qgcm_clear_keys(ctx, ctx->dtls_slots[2ull * p + d], 1);
+            if (r != QGCM_OK) rc = r;
+        }
+    }
+    return rc;
+}
+
+int qgcm_dtls_session_state(qgcm_ctx *ctx, uint32_t session, uint64_t out[4]) {
+    if (!ctx || !out) return QGCM_E_ARG;
+    if (session >= ctx->max_keys) return QGCM_E_KEY;
+    if (hipSetDevice(ctx->device) != hipSuccess) return QGCM_E_HIP;
+    std::lock_guard<std::mutex> lk(ctx->dtls_mu);
+    DtlsSession t{};
+    if (ctx->d_dtls && (hipDeviceSynchronize() != hipSuccess ||
+                        hipMemcpy(&t, ctx->d_dtls + session, sizeof t, hipMemcpyDeviceToHost) != hipSuccess))
+        return QGCM_E_HIP;
+    out[0] = t.write_seq;
+    out[1] = t.R;
+    out[2] = t.W;
+    out[3] = t.set;
+    return QGCM_OK;
+}
+
+int qgcm_dtls_seal(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                   const uint32_t *d_peer, qgcm_dtls_hdr *d_hdr, uint8_t *d_status, uint8_t *d_reason, void *stream) {
+    return dtls_run(ctx, true, d_arena, stride, n, d_lens, d_peer, d_hdr, d_status, d_reason, (hipStream_t)stream);
+}
+
+int qgcm_dtls_open(qgcm_ctx *ctx, uint8_t *d_arena, uint64_t stride, uint32_t n, uint32_t *d_lens,
+                   const uint32_t *d_peer, const qgcm_dtls_hdr *d_hdr, uint8_t *d_status, uint8_t *d_reason,
+                   void *stream) {
+    return dtls_run(ctx, false, d_arena, stride, n, d_lens, d_peer, const_cast<qgcm_dtls_hdr *>(d_hdr), d_status,
+                    d_reason, (hipStream_t)stream);
 }
 
 }  // extern "C"

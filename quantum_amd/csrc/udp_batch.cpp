@@ -618,4 +618,112 @@ int qgcm_train_pack_cpu(const uint8_t *arena, uint64_t stride, uint32_t n, const
     return QGCM_OK;
 }
 
+// Split DTLS records (include/qgcm.h "DTLS 1.2 records on routed batches"), one record per datagram: the 21
+// bytes of hdr[i] in front of Raw[:lens[i]] of slot i by a second iovec, so neither side copies a record
+// together.  To addrs[peer[i]] for the slots with status 1, as qgcm_udp_send_slots_to.
+int qgcm_udp_send_dtls(int fd, const uint8_t *arena, uint64_t stride, uint32_t n, const uint32_t *lens,
+                       const qgcm_dtls_hdr *hdr, const uint8_t *status, const uint32_t *peer,
+                       const qgcm_peer_addr *addrs, uint32_t n_addrs) {
+    if (fd < 0 || (n && (!arena || !lens || !hdr || !peer)) || (n_addrs && !addrs)) return -1;
+    auto skip = [&](uint32_t i) { return (status && status[i] != 1) || peer[i] == QGCM_NO_PEER || lens[i] == 0; };
+    for (uint32_t i = 0; i < n; ++i)
+        if (!skip(i) && peer[i] >= n_addrs) return -1;
+    std::vector<mmsghdr> msgs(kVlen);
+    std::vector<iovec> iov(2 * kVlen);
+    std::vector<sockaddr_in> dst(kVlen);
+    uint32_t next = 0, sent = 0;
+    while (next < n) {
+        unsigned k = 0;
+        for (; next < n && k < kVlen; ++next) {
+            if (skip(next)) continue;
+            const qgcm_peer_addr &a = addrs[peer[next]];
+            memset(&dst[k], 0, sizeof dst[k]);
+            dst[k].sin_family = AF_INET;
+            dst[k].sin_addr.s_addr = a.ip;  // network byte order already
+            dst[k].sin_port = a.port;
+            iov[2 * k] = iovec{const_cast<uint8_t *>(hdr[next].b), (size_t)QGCM_DTLS_HDR_BYTES};
+            iov[2 * k + 1] = iovec{const_cast<uint8_t *>(arena) + (uint64_t)next * stride,
+                                   (size_t)std::min<uint64_t>(lens[next], stride)};
+            msgs[k] = mmsghdr{};
+            msgs[k].msg_hdr.msg_name = &dst[k];
+            msgs[k].msg_hdr.msg_namelen = sizeof dst[k];
+            msgs[k].msg_hdr.msg_iov = &iov[2 * k];
+            msgs[k].msg_hdr.msg_iovlen = 2;
+            ++k;
+        }
+        for (unsigned done = 0; done < k;) {
+            const int r = sendmmsg(fd, msgs.data() + done, k - done, 0);
+            if (r < 0) {
+                if (errno == EINTR) continue;
+                return sent ? (int)sent : -1;
+            }
+            done += (unsigned)r;
+            sent += (uint32_t)r;
+        }
+    }
+    return (int)sent;
+}
+
+// The receiving side: datagram -> hdr[i].b[0:21] and Raw[0:lens[i]] of slot i, the sender to addrs_out[i].  A
+// datagram that cannot be a record in a slot (under 22 bytes, or longer than 21 + stride: the kernel marks it
+// truncated) is dropped and counted; the slots filled stay dense.
+int qgcm_udp_recv_dtls(int fd, uint8_t *arena, uint64_t stride, uint32_t max_n, uint32_t *lens, qgcm_dtls_hdr *hdr,
+                       qgcm_peer_addr *addrs_out, int timeout_ms, uint32_t *dropped) {
+    if (dropped) *dropped = 0;
+    if (fd < 0 || (max_n && (!arena || !lens || !hdr)) || stride == 0) return -1;
+    if (max_n == 0) return 0;
+    pollfd p{fd, POLLIN, 0};
+    int pr;
+    do {
+        pr = poll(&p, 1, timeout_ms);
+    } while (pr < 0 && errno == EINTR);
+    if (pr < 0) return -1;
+    if (pr == 0) return 0;
+    const size_t vlen = std::min<uint32_t>(max_n, kVlen);
+    std::vector<mmsghdr> msgs(vlen);
+    std::vector<iovec> iov(2 * vlen);
+    std::vector<sockaddr_in> src(vlen);
+    uint32_t got = 0, lost = 0;
+    while (got < max_n) {
+        const unsigned k = (unsigned)std::min<uint64_t>(max_n - got, vlen);
+        for (unsigned i = 0; i < k; ++i) {
+            iov[2 * i] = iovec{hdr[got + i].b, (size_t)QGCM_DTLS_HDR_BYTES};
+            iov[2 * i + 1] = iovec{arena + (uint64_t)(got + i) * stride, (size_t)stride};
+            msgs[i] = mmsghdr{};
+            msgs[i].msg_hdr.msg_name = &src[i];
+            msgs[i].msg_hdr.msg_namelen = sizeof src[i];
+            msgs[i].msg_hdr.msg_iov = &iov[2 * i];
+            msgs[i].msg_hdr.msg_iovlen = 2;
+        }
+        const int r = recvmmsg(fd, msgs.data(), k, MSG_DONTWAIT, nullptr);
+        if (r < 0) {
+            if (errno == EINTR) continue;
+            if (errno == EAGAIN || errno == EWOULDBLOCK) break;
+            if (dropped) *dropped = lost;
+            return got ? (int)got : -1;
+        }
+        uint32_t kept = 0;  // of this round: message i moves down to slot got + kept
+        for (int i = 0; i < r; ++i) {
+            const uint32_t len = msgs[i].msg_len;
+            if (len <= QGCM_DTLS_HDR_BYTES || (msgs[i].msg_hdr.msg_flags & MSG_TRUNC)) {
+                ++lost;
+                continue;
+            }
+            const uint32_t to = got + kept, from = got + (uint32_t)i, body = len - QGCM_DTLS_HDR_BYTES;
+            if (to != from) {
+                memcpy(hdr[to].b, hdr[from].b, QGCM_DTLS_HDR_BYTES);
+                memcpy(arena + (uint64_t)to * stride, arena + (uint64_t)from * stride, body);
+            }
+            memset(hdr[to].b + QGCM_DTLS_HDR_BYTES, 0, sizeof hdr[to].b - QGCM_DTLS_HDR_BYTES);
+            lens[to] = body;
+            if (addrs_out) addrs_out[to] = qgcm_peer_addr{src[i].sin_addr.s_addr, src[i].sin_port, 0};
+            ++kept;
+        }
+        got += kept;
+        if ((unsigned)r < k) break;
+    }
+    if (dropped) *dropped = lost;
+    return (int)got;
+}
+
 }  // extern "C"
