@@ -61,11 +61,12 @@ struct RouteState {
     // chunk of 65536 slots gives it 1024 waves where the unpack has 16384
     bool gro_fused = false;
 
-    // the coalesced-receive pipelines: a chunk's table and packed bytes on the device, the rebased table on
-    // the host (under pipe_mu, on `stream`)
-    uint8_t *d_gro = nullptr;
-    size_t gro_cap = 0;
-    std::vector<qgcm_gro_buf> h_gro;
+    // the pipelines whose batch arrives packed (coalesced buffers, frames, super-frames): a chunk's table and
+    // packed bytes on the device, the rebased table on the host (under pipe_mu, on `stream`; one call at a time,
+    // so one area serves the three forms)
+    uint8_t *d_stage = nullptr;
+    size_t stage_cap = 0;
+    std::vector<uint8_t> h_stage;
 
     // the packed pipelines: a chunk's records, counts, scan work area and packed bytes on the device (under
     // pipe_mu, on `stream`)
@@ -76,18 +77,6 @@ struct RouteState {
     // device (under pipe_mu, on `stream`)
     uint8_t *d_train = nullptr;
     size_t train_cap = 0;
-
-    // the packed-frames pipeline: a chunk's table and packed bytes on the device, the rebased table on the host
-    // (under pipe_mu, on `stream`)
-    uint8_t *d_frames = nullptr;
-    size_t frames_cap = 0;
-    std::vector<qgcm_frame> h_frames;
-
-    // the super-frame pipeline: a chunk's table and packed bytes on the device, the rebased table on the host
-    // (under pipe_mu, on `stream`)
-    uint8_t *d_gso = nullptr;
-    size_t gso_cap = 0;
-    std::vector<qgcm_gso_frame> h_gso;
 };
 
 RouteState *route_state_create() {
@@ -107,11 +96,9 @@ void route_state_destroy(RouteState *r) {
     hipFree(r->d_arena);
     hipFree(r->d_side);
     hipFree(r->d_plan);
-    hipFree(r->d_gro);
+    hipFree(r->d_stage);
     hipFree(r->d_pack);
     hipFree(r->d_train);
-    hipFree(r->d_frames);
-    hipFree(r->d_gso);
     if (r->stream) hipStreamDestroy(r->stream);
     delete r;
 }
@@ -566,414 +553,379 @@ void train_rebase(TrainOut &tk, uint32_t c0, uint32_t cn) {
     tk.out[3] = tk.m;
 }
 
-// Outgoing.pipeline / Incoming.pipeline for a batch in host memory: chunks of at most kRouteChunk packets,
-// copy in -> resolve -> seal or open (chain: the plugin chain under the node's `plugins`) -> account -> copy
-// back, on one stream.  With `pk` (the incoming chain only) the copy back is the packed one: the pack runs
-// behind the chain, its counts are waited for before the chunk is accounted, and the arena stays on the device.
-// With `tk` (the outgoing chain only) the same for the planned trains: plan and train pack run behind the chain.
+// The PackOut of a packed call (h_table: qgcm_pack_rec) or a coalesced one (qgcm_gso_frame), its `out` zeroed;
+// false: an argument is missing.
+bool pack_out(PackOut &pk, bool coalesced, uint32_t n, uint8_t *h_out, uint64_t out_cap, void *h_table, uint64_t *out) {
+    if (!out || (n && (!h_out || !h_table))) return false;
+    std::fill(out, out + (coalesced ? 5 : 3), 0);
+    pk = PackOut{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), coalesced ? nullptr : static_cast<qgcm_pack_rec *>(h_table), out};
+    if (coalesced) pk.h_frames = static_cast<qgcm_gso_frame *>(h_table);
+    return true;
+}
+
+// The TrainOut of a packed outgoing call, its `out` zeroed; false: an argument is missing or the limits are invalid.
+bool train_out(TrainOut &tk, uint32_t n, uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order,
+               const qgcm_plan_limits *limits, uint64_t *out) {
+    if (!out || (n && (!h_out || !h_ptrains))) return false;
+    std::fill(out, out + 4, 0);
+    tk = TrainOut{h_out, std::min<uint64_t>(out_cap, kTrainMaxCap), h_ptrains, h_order, out};
+    return plan_limits_resolve(limits, &tk.lim);
+}
+
+// The routed host pipelines: Outgoing.pipeline / Incoming.pipeline for a batch in host memory, in chunks of at
+// most kRouteChunk packets and kRouteChunkBytes of slots, on one stream.  Four front ends, one per form the batch
+// arrives in -- slots (run_route_host), coalesced buffers (run_route_gro_host), packed frames
+// (run_route_frames_host), super-frames (run_route_gso_host) -- differ in how they cut the chunks and in what goes
+// up.  Each reads: its checks, pipe_enter, the chunks cut, chunk_grow (and stage_grow), then per chunk the table
+// rebased, the copy in, the resolve, and chunk_tail for everything behind it.
+
+// What a pipeline holds from pipe_enter on: the pipeline lock, the routed stream, the most slots a chunk takes.
+struct Pipe {
+    std::unique_lock<std::mutex> lock;
+    hipStream_t s = nullptr;
+    uint32_t limit = 0;
+};
+
+// the routed stream, made by the first call that needs it (under pipe_mu); NULL when it cannot be made
+hipStream_t pipe_stream(RouteState *r) {
+    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) r->stream = nullptr;
+    return r->stream;
+}
+
+// The entry of a pipeline, behind the front end's own argument and table checks: the routes are set; for n == 0
+// that is all (QGCM_OK: the caller returns it); else the pipeline lock, the device, the stream, the chunk limit.
+int pipe_enter(qgcm_ctx *ctx, uint64_t stride, uint32_t n, Pipe &p) {
+    RouteState *r = ctx_route(ctx);
+    {
+        std::lock_guard<std::mutex> g(r->mu);
+        if (!r->set) return QGCM_E_ARG;
+    }
+    if (n == 0) return QGCM_OK;
+    p.lock = std::unique_lock<std::mutex>(r->pipe_mu);
+    if (hipSetDevice(ctx_device(ctx)) != hipSuccess || !(p.s = pipe_stream(r))) return QGCM_E_HIP;
+    p.limit = (uint32_t)std::min<uint64_t>(kRouteChunk, std::max<uint64_t>(1, kRouteChunkBytes / stride));
+    return QGCM_OK;
+}
+
+// The side buffer of a chunk, in r->d_side: descriptors (16-B aligned first), lengths, peers, nonces, statuses;
+// with the chain its byte counts and its work area (16-B aligned) behind them.  One layout for every pipeline:
+// the coalesced-receive ones, which seal nothing, leave the nonces unused.
+struct Side {
+    qgcm_desc *d_descs;
+    uint32_t *d_lens, *d_peer;
+    uint8_t *d_non, *d_stat;
+    uint32_t *d_bytes;  // NULL without the chain, as d_work
+    void *d_work;
+};
+
+// The device areas of a call whose chunks have at most max_cn slots: the arena, the side buffer (laid out here and
+// nowhere else), the statuses' host copy, and the areas of `pk` / `tk`.
+bool chunk_grow(RouteState *r, Side &sd, uint32_t max_cn, uint64_t stride, bool chain, PackOut *pk, TrainOut *tk) {
+    const size_t o_desc = 0, o_lens = o_desc + 16ull * max_cn, o_peer = o_lens + 4ull * max_cn, o_non = o_peer + 4ull * max_cn,
+                 o_stat = o_non + 12ull * max_cn, o_bytes = (o_stat + max_cn + 15) & ~(size_t)15,
+                 o_work = o_bytes + 4 * (size_t)chain_work_lanes(max_cn),
+                 side = chain ? o_work + QGCM_CHAIN_WORK(max_cn) : o_stat + max_cn;
+    if (!grow(r->d_arena, r->arena_cap, (size_t)max_cn * stride) || !grow(r->d_side, r->side_cap, side) ||
+        (pk && !pack_grow(r, *pk, max_cn, stride)) || (tk && !train_grow(r, *tk, max_cn, stride)))
+        return false;
+    r->h_stat.resize(max_cn);
+    uint8_t *d = r->d_side;
+    sd = Side{reinterpret_cast<qgcm_desc *>(d + o_desc), reinterpret_cast<uint32_t *>(d + o_lens),
+              reinterpret_cast<uint32_t *>(d + o_peer), d + o_non, d + o_stat,
+              chain ? reinterpret_cast<uint32_t *>(d + o_bytes) : nullptr, chain ? d + o_work : nullptr};
+    return true;
+}
+
+// The ingest staging of a call whose batch arrives packed, in r->d_stage: a chunk's table of at most max_entries
+// entries (16-B aligned first), then its span of at most max_span packed bytes (16-B aligned, rounded up to 16 B);
+// the table's host copy, where the front end rebases it, in r->h_stage.
+template <typename T>
+bool stage_grow(RouteState *r, uint32_t max_entries, uint64_t max_span, T *&h_tab, T *&d_tab, uint8_t *&d_packed) {
+    const size_t table = sizeof(T) * (size_t)max_entries, o_packed = (table + 15) & ~(size_t)15;
+    if (!grow(r->d_stage, r->stage_cap, std::max<size_t>(o_packed + (size_t)((max_span + 15) & ~(uint64_t)15), 16))) return false;
+    r->h_stage.resize(table);
+    h_tab = reinterpret_cast<T *>(r->h_stage.data());
+    d_tab = reinterpret_cast<T *>(r->d_stage);
+    d_packed = r->d_stage + o_packed;
+    return true;
+}
+
+// A chunk that ends at a table-entry boundary: entries [e0, e1), slots [c0, c0 + cn), packed bytes [lo, hi).
+struct Chunk {
+    uint32_t e0, e1, c0, cn;
+    uint64_t lo, hi;
+};
+
+// ... and the chunks of a call, with what sizes the device areas
+struct Chunks {
+    std::vector<Chunk> v;
+    uint32_t max_cn = 0, max_entries = 0;
+    uint64_t max_span = 0;
+    void add(Chunk c) {
+        if (c.lo > c.hi) c.lo = c.hi = 0;  // no entry of it has bytes that go up
+        max_cn = std::max(max_cn, c.cn);
+        max_entries = std::max(max_entries, c.e1 - c.e0);
+        max_span = std::max(max_span, c.hi - c.lo);
+        v.push_back(c);
+    }
+};
+
+// What the chunks of one call share behind their resolve.
+struct Job {
+    qgcm_ctx *ctx;
+    hipStream_t s;
+    bool seal, chain;
+    uint32_t plugins;  // of the chain
+    uint64_t stride;
+    uint32_t *h_lens, *h_peer;
+    uint8_t *h_status;  // may be NULL
+    bool lens_back;     // the lengths come down: the chain's are final on the device (the tables of include/qgcm.h),
+                        // and an ingest kernel's exist nowhere else
+    PackOut *pk;        // the incoming chain only: the copy back is the packed one, the arena stays on the device
+    TrainOut *tk;       // the outgoing chain only: the same for the planned trains
+    int dropped = 0;
+};
+
+// A chunk from "arena, lengths, peers and descriptors are resolved on the device" (rc: how the front end's copy in
+// and resolve went) to "the host outputs are final": seal or open (chain: the plugin chain, then with `pk` / `tk`
+// the pack or the plan and train pack, whose counts are waited for before the chunk is accounted) -> account ->
+// copy back (h_dst: where the arena goes, unused with `pk` / `tk`) -> wait -> rebase -> statuses and lengths.
+// `nonces` is on the device, QGCM_NONCES_GENERATE or NULL.
+int chunk_tail(Job &j, const Side &sd, int rc, uint32_t c0, uint32_t cn, const uint8_t *nonces, uint8_t *h_dst) {
+    RouteState *r = ctx_route(j.ctx);
+    hipStream_t s = j.s;
+    const int dir = j.seal ? QGCM_TX : QGCM_RX;
+    if (rc == QGCM_OK && j.chain) {
+        rc = run_chain(j.ctx, j.seal, r->d_arena, j.stride, cn, sd.d_lens, sd.d_peer, sd.d_descs, j.plugins, nonces, sd.d_stat,
+                       sd.d_bytes, sd.d_work, s);
+        if (rc == QGCM_OK && j.pk) rc = pack_chunk(*j.pk, r->d_arena, j.stride, c0, cn, sd.d_lens, sd.d_peer, sd.d_stat, s);
+        if (rc == QGCM_OK && j.tk)
+            rc = train_chunk(*j.tk, ctx_max_keys(j.ctx), r->d_arena, j.stride, c0, cn, sd.d_lens, sd.d_peer, s);
+        if (rc == QGCM_OK) rc = account(j.ctx, dir, cn, sd.d_peer, nullptr, sd.d_bytes, true, sd.d_stat, s);
+    } else if (rc == QGCM_OK) {
+        rc = j.seal ? qgcm_seal_batch(j.ctx, r->d_arena, sd.d_descs, cn, nonces, 4, sd.d_stat, s)
+                    : qgcm_open_batch(j.ctx, r->d_arena, sd.d_descs, cn, 4, sd.d_stat, s);
+        if (rc == QGCM_OK) rc = qgcm_route_account(j.ctx, dir, cn, sd.d_peer, sd.d_descs, sd.d_stat, s);
+    }
+    if (rc == QGCM_OK &&
+        ((j.pk   ? !pack_copy_back(*j.pk, s)
+          : j.tk ? !train_copy_back(*j.tk, s)
+                 : hipMemcpyAsync(h_dst, r->d_arena, (size_t)cn * j.stride, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+         hipMemcpyAsync(j.h_peer + c0, sd.d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+         hipMemcpyAsync(r->h_stat.data(), sd.d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
+         (j.lens_back && hipMemcpyAsync(j.h_lens + c0, sd.d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess)))
+        rc = QGCM_E_HIP;
+    // every way out waits for the stream: the next call reuses the staging, and the caller its arrays
+    if (hipStreamSynchronize(s) != hipSuccess && rc == QGCM_OK) rc = QGCM_E_HIP;
+    if (rc != QGCM_OK) return rc;
+    if (j.pk) pack_rebase(*j.pk, c0, cn);
+    if (j.tk) train_rebase(*j.tk, c0, cn);
+    for (uint32_t i = 0; i < cn; ++i) {
+        const bool ok = r->h_stat[i] == 1;
+        if (!j.chain) {
+            // from the length that went in (the caller's, or the datagram's that came down from an ingest kernel).
+            // Sealed: the datagram Raw[:4 + L + 28]; opened: the plaintext packet qgcm_tun_write_slots takes
+            const uint32_t len = j.h_lens[c0 + i];
+            j.h_lens[c0 + i] = !ok ? 0 : j.seal ? 4 + len + QGCM_OVERHEAD : len - 4 - QGCM_OVERHEAD;
+        }
+        if (j.h_status) j.h_status[c0 + i] = ok ? 1 : 0;
+        j.dropped += !ok;
+    }
+    return QGCM_OK;
+}
+
+// The batch in slots of the caller's arena: chunks of a fixed number of slots; a chunk's slots, lengths and (seal,
+// the caller's) nonces go up and the resolve kernel resolves them.
 int run_route_host(qgcm_ctx *ctx, bool seal, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens,
                    const uint8_t *h_nonces, uint32_t *h_peer, uint8_t *h_status, bool chain = false,
                    uint32_t plugins = 0, PackOut *pk = nullptr, TrainOut *tk = nullptr) {
     if (!ctx) return QGCM_E_ARG;
-    RouteState *r = ctx_route(ctx);
     if ((stride & 3) || n > QGCM_MAX_BATCH) return QGCM_E_ARG;
     if (n && (!h_arena || !h_lens || !h_peer || stride == 0)) return QGCM_E_ARG;
     if (chain && (plugins & ~kAllPlugins)) return QGCM_E_ARG;
-    {
-        std::lock_guard<std::mutex> g(r->mu);
-        if (!r->set) return QGCM_E_ARG;
-    }
-    if (n == 0) return 0;
-    const bool gen = seal && h_nonces == QGCM_NONCES_GENERATE;
-    const bool non = seal && h_nonces && !gen;
-    std::lock_guard<std::mutex> pg(r->pipe_mu);
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
-    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
-        r->stream = nullptr;
-        return QGCM_E_HIP;
-    }
-    hipStream_t s = r->stream;
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(kRouteChunk, n),
-                                                        std::max<uint64_t>(1, kRouteChunkBytes / stride));
-    // side buffer of a chunk: descriptors (16-B aligned first), lengths, peers, nonces, statuses; the chain's
-    // byte counts and its work area (16-B aligned) behind them
-    const size_t o_desc = 0, o_lens = o_desc + 16ull * chunk, o_peer = o_lens + 4ull * chunk,
-                 o_non = o_peer + 4ull * chunk, o_stat = o_non + 12ull * chunk,
-                 o_bytes = (o_stat + chunk + 15) & ~(size_t)15, o_work = o_bytes + 4 * (size_t)chain_work_lanes(chunk),
-                 side = chain ? o_work + QGCM_CHAIN_WORK(chunk) : o_stat + chunk;
-    if (!grow(r->d_arena, r->arena_cap, (size_t)chunk * stride) || !grow(r->d_side, r->side_cap, side)) return QGCM_E_NOMEM;
-    if (pk && !pack_grow(r, *pk, chunk, stride)) return QGCM_E_NOMEM;
-    if (tk && !train_grow(r, *tk, chunk, stride)) return QGCM_E_NOMEM;
-    r->h_stat.resize(chunk);
-    qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
-    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
-    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
-    uint8_t *d_non = r->d_side + o_non, *d_stat = r->d_side + o_stat;
-    uint32_t *d_bytes = reinterpret_cast<uint32_t *>(r->d_side + o_bytes);
-    int dropped = 0;
+    Pipe p;
+    int rc = pipe_enter(ctx, stride, n, p);
+    if (rc != QGCM_OK || n == 0) return rc;
+    RouteState *r = ctx_route(ctx);
+    const bool gen = seal && h_nonces == QGCM_NONCES_GENERATE, non = seal && h_nonces && !gen;
+    const uint32_t chunk = std::min(p.limit, n);
+    Side sd;
+    if (!chunk_grow(r, sd, chunk, stride, chain, pk, tk)) return QGCM_E_NOMEM;
+    Job job{ctx, p.s, seal, chain, plugins, stride, h_lens, h_peer, h_status, chain, pk, tk};
     for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
         const uint32_t cn = std::min(chunk, n - c0);
         uint8_t *h = h_arena + (uint64_t)c0 * stride;
-        if (hipMemcpyAsync(r->d_arena, h, (size_t)cn * stride, hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(d_lens, h_lens + c0, 4ull * cn, hipMemcpyHostToDevice, s) != hipSuccess ||
-            (non && hipMemcpyAsync(d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, s) != hipSuccess))
-            return QGCM_E_HIP;
-        int rc = resolve(ctx, seal, r->d_arena, stride, cn, d_lens, d_peer, d_descs, s);
-        const uint8_t *nonces = gen ? QGCM_NONCES_GENERATE : non ? d_non : nullptr;
-        if (rc == QGCM_OK && chain) {
-            rc = run_chain(ctx, seal, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, nonces, d_stat, d_bytes,
-                           r->d_side + o_work, s);
-            if (rc == QGCM_OK && pk) rc = pack_chunk(*pk, r->d_arena, stride, c0, cn, d_lens, d_peer, d_stat, s);
-            if (rc == QGCM_OK && tk) rc = train_chunk(*tk, ctx_max_keys(ctx), r->d_arena, stride, c0, cn, d_lens, d_peer, s);
-            if (rc == QGCM_OK) rc = account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
-        } else if (rc == QGCM_OK) {
-            rc = seal ? qgcm_seal_batch(ctx, r->d_arena, d_descs, cn, nonces, 4, d_stat, s)
-                      : qgcm_open_batch(ctx, r->d_arena, d_descs, cn, 4, d_stat, s);
-            if (rc == QGCM_OK) rc = qgcm_route_account(ctx, seal ? QGCM_TX : QGCM_RX, cn, d_peer, d_descs, d_stat, s);
-        }
-        if (rc == QGCM_OK &&
-            ((pk   ? !pack_copy_back(*pk, s)
-              : tk ? !train_copy_back(*tk, s)
-                   : hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-             hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             // the chain's lengths are final on the device (the tables of include/qgcm.h)
-             (chain && hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess)))
-            rc = QGCM_E_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
+        const bool up = hipMemcpyAsync(r->d_arena, h, (size_t)cn * stride, hipMemcpyHostToDevice, p.s) == hipSuccess &&
+                        hipMemcpyAsync(sd.d_lens, h_lens + c0, 4ull * cn, hipMemcpyHostToDevice, p.s) == hipSuccess &&
+                        (!non || hipMemcpyAsync(sd.d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, p.s) == hipSuccess);
+        rc = up ? resolve(ctx, seal, r->d_arena, stride, cn, sd.d_lens, sd.d_peer, sd.d_descs, p.s) : QGCM_E_HIP;
+        rc = chunk_tail(job, sd, rc, c0, cn, gen ? QGCM_NONCES_GENERATE : non ? sd.d_non : nullptr, h);
         if (rc != QGCM_OK) return rc;
-        if (pk) pack_rebase(*pk, c0, cn);
-        if (tk) train_rebase(*tk, c0, cn);
-        for (uint32_t i = 0; i < cn; ++i) {
-            const bool ok = r->h_stat[i] == 1;
-            if (chain) {
-                if (h_status) h_status[c0 + i] = ok ? 1 : 0;
-                dropped += !ok;
-                continue;
-            }
-            const uint32_t len = h_lens[c0 + i];
-            // sealed: the datagram Raw[:4 + L + 28]; opened: the plaintext packet qgcm_tun_write_slots takes
-            h_lens[c0 + i] = !ok ? 0 : seal ? 4 + len + QGCM_OVERHEAD : len - 4 - QGCM_OVERHEAD;
-            if (h_status) h_status[c0 + i] = ok ? 1 : 0;
-            dropped += !ok;
-        }
     }
-    return dropped;
+    return job.dropped;
 }
 
-// Incoming.pipeline for a batch that arrived as coalesced buffers (qgcm_udp_recv_gro): run_route_host's open
-// side with the copy-in replaced.  Chunks end at buffer boundaries; per chunk the packed bytes its buffers
-// span and their table entries (rebased to the span and to the chunk's first slot) go up, gro_unpack_kernel
-// scatters them into the device arena and the resolve kernel resolves them (QGCM_GRO_FUSED=1: gro_resolve_kernel
-// does both), and open or chain, accounting and the copy back follow as in run_route_host.  The lengths start as zeros on the device, so the slots of a buffer the kernel skips (one
-// past packed_len) are datagrams of length 0.
+// The batch in coalesced buffers (qgcm_udp_recv_gro), incoming only.  Chunks end at buffer boundaries, and lo is
+// aligned down to 16 B.  Per chunk the packed bytes its buffers span and their table entries (rebased to the span
+// and to the chunk's first slot) go up; gro_unpack_kernel scatters them into the device arena and the resolve
+// kernel resolves them (QGCM_GRO_FUSED=1: gro_resolve_kernel does both).  The lengths start as zeros on the
+// device, so the slots of a buffer the kernel skips (one past packed_len) are datagrams of length 0.
 int run_route_gro_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gro_buf *bufs,
                        uint32_t n_bufs, uint8_t *h_arena, uint64_t stride, uint32_t n, uint32_t *h_lens, uint32_t *h_peer,
                        uint8_t *h_status, bool chain, uint32_t plugins, PackOut *pk = nullptr) {
     if (!ctx) return QGCM_E_ARG;
-    RouteState *r = ctx_route(ctx);
     if ((stride & 3) || n > QGCM_MAX_BATCH || n_bufs > n) return QGCM_E_ARG;
     if (n && (!h_packed || !bufs || (!h_arena && !pk) || !h_lens || !h_peer || stride == 0)) return QGCM_E_ARG;
     if (chain && (plugins & ~kAllPlugins)) return QGCM_E_ARG;
     if (!gro_table_ok(bufs, n_bufs, n)) return QGCM_E_ARG;
-    {
-        std::lock_guard<std::mutex> g(r->mu);
-        if (!r->set) return QGCM_E_ARG;
-    }
-    if (n == 0) return 0;
-    std::lock_guard<std::mutex> pg(r->pipe_mu);
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
-    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
-        r->stream = nullptr;
-        return QGCM_E_HIP;
-    }
-    hipStream_t s = r->stream;
-    const uint32_t limit = (uint32_t)std::min<uint64_t>(kRouteChunk, std::max<uint64_t>(1, kRouteChunkBytes / stride));
-    // the chunks: buffers [b0, b1), slots [c0, c0 + cn), packed bytes [lo, hi) (lo on a 16-B boundary)
-    struct Chunk {
-        uint32_t b0, b1, c0, cn;
-        uint64_t lo, hi;
-    };
-    std::vector<Chunk> chunks;
-    uint32_t max_cn = 0, max_nb = 0;
-    uint64_t max_span = 0;
+    Pipe p;
+    int rc = pipe_enter(ctx, stride, n, p);
+    if (rc != QGCM_OK || n == 0) return rc;
+    RouteState *r = ctx_route(ctx);
+    Chunks chunks;
     for (uint32_t b = 0; b < n_bufs;) {
         Chunk c{b, b, bufs[b].first, 0, UINT64_MAX, 0};
         for (; b < n_bufs; ++b) {
             const uint32_t count = (uint32_t)gro_count(bufs[b].len, bufs[b].seg_len);  // at most n: the table is checked
-            if (c.cn && (uint64_t)c.cn + count > limit) break;
+            if (c.cn && (uint64_t)c.cn + count > p.limit) break;
             c.cn += count;
             if ((uint64_t)bufs[b].off + bufs[b].len > packed_len) continue;  // skipped by the kernel: none of its bytes go up
             c.lo = std::min<uint64_t>(c.lo, bufs[b].off & ~15u);
             c.hi = std::max<uint64_t>(c.hi, (uint64_t)bufs[b].off + bufs[b].len);
         }
-        c.b1 = b;
-        if (c.lo > c.hi) c.lo = c.hi = 0;
-        max_cn = std::max(max_cn, c.cn);
-        max_nb = std::max(max_nb, c.b1 - c.b0);
-        max_span = std::max(max_span, c.hi - c.lo);
-        chunks.push_back(c);
+        c.e1 = b;
+        chunks.add(c);
     }
-    // side buffer of a chunk as in run_route_host (no nonces); the table (16-B aligned) and the packed bytes
-    // (16-B aligned, rounded up to 16 B) in a staging area of their own
-    const size_t o_desc = 0, o_lens = o_desc + 16ull * max_cn, o_peer = o_lens + 4ull * max_cn, o_stat = o_peer + 4ull * max_cn,
-                 o_bytes = (o_stat + max_cn + 15) & ~(size_t)15, o_work = o_bytes + 4 * (size_t)chain_work_lanes(max_cn),
-                 side = chain ? o_work + QGCM_CHAIN_WORK(max_cn) : o_stat + max_cn;
-    const size_t o_packed = 16ull * max_nb, gro = o_packed + (size_t)((max_span + 15) & ~(uint64_t)15);
-    if (!grow(r->d_arena, r->arena_cap, (size_t)max_cn * stride) || !grow(r->d_side, r->side_cap, side) ||
-        !grow(r->d_gro, r->gro_cap, std::max<size_t>(gro, 16)) || (pk && !pack_grow(r, *pk, max_cn, stride)))
+    Side sd;
+    qgcm_gro_buf *h_bufs, *d_bufs;
+    uint8_t *d_packed;
+    if (!chunk_grow(r, sd, chunks.max_cn, stride, chain, pk, nullptr) ||
+        !stage_grow(r, chunks.max_entries, chunks.max_span, h_bufs, d_bufs, d_packed))
         return QGCM_E_NOMEM;
-    r->h_stat.resize(max_cn);
-    r->h_gro.resize(max_nb);
-    qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
-    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
-    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
-    uint8_t *d_stat = r->d_side + o_stat;
-    uint32_t *d_bytes = reinterpret_cast<uint32_t *>(r->d_side + o_bytes);
-    qgcm_gro_buf *d_bufs = reinterpret_cast<qgcm_gro_buf *>(r->d_gro);
-    uint8_t *d_packed = r->d_gro + o_packed;
-    int dropped = 0;
-    for (const Chunk &c : chunks) {
-        const uint32_t nb = c.b1 - c.b0, cn = c.cn, c0 = c.c0;
+    Job job{ctx, p.s, false, chain, plugins, stride, h_lens, h_peer, h_status, true, pk, nullptr};
+    for (const Chunk &c : chunks.v) {
+        const uint32_t nb = c.e1 - c.e0;
         for (uint32_t j = 0; j < nb; ++j) {
-            const qgcm_gro_buf &b = bufs[c.b0 + j];
+            const qgcm_gro_buf &b = bufs[c.e0 + j];
             const bool past = (uint64_t)b.off + b.len > packed_len;
             // a buffer past packed_len stays one the kernel skips: its one entry keeps the search over `first` whole
-            r->h_gro[j] = past ? qgcm_gro_buf{0xffffffffu, 1, 0, b.first - c0}
-                               : qgcm_gro_buf{(uint32_t)(b.off - c.lo), b.len, b.seg_len, b.first - c0};
+            h_bufs[j] = past ? qgcm_gro_buf{0xffffffffu, 1, 0, b.first - c.c0}
+                             : qgcm_gro_buf{(uint32_t)(b.off - c.lo), b.len, b.seg_len, b.first - c.c0};
         }
-        uint8_t *h = pk ? nullptr : h_arena + (uint64_t)c0 * stride;
-        if (hipMemsetAsync(d_lens, 0, 4ull * cn, s) != hipSuccess ||
-            (c.hi > c.lo && hipMemcpyAsync(d_packed, h_packed + c.lo, (size_t)(c.hi - c.lo), hipMemcpyHostToDevice, s) != hipSuccess) ||
-            hipMemcpyAsync(d_bufs, r->h_gro.data(), 16ull * nb, hipMemcpyHostToDevice, s) != hipSuccess)
-            return QGCM_E_HIP;
-        int rc;
-        if (r->gro_fused) {
-            rc = gro_resolve(ctx, d_packed, c.hi - c.lo, d_bufs, nb, cn, r->d_arena, stride, d_lens, d_peer, d_descs, s);
-        } else {
-            rc = hip_rc(launch_gro_unpack(d_packed, c.hi - c.lo, d_bufs, nb, cn, r->d_arena, stride, d_lens, s));
-            if (rc == QGCM_OK) rc = resolve(ctx, false, r->d_arena, stride, cn, d_lens, d_peer, d_descs, s);
-        }
-        if (rc == QGCM_OK && chain) {
-            rc = run_chain(ctx, false, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, nullptr, d_stat, d_bytes,
-                           r->d_side + o_work, s);
-            if (rc == QGCM_OK && pk) rc = pack_chunk(*pk, r->d_arena, stride, c0, cn, d_lens, d_peer, d_stat, s);
-            if (rc == QGCM_OK) rc = account(ctx, QGCM_RX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
-        } else if (rc == QGCM_OK) {
-            rc = qgcm_open_batch(ctx, r->d_arena, d_descs, cn, 4, d_stat, s);
-            if (rc == QGCM_OK) rc = qgcm_route_account(ctx, QGCM_RX, cn, d_peer, d_descs, d_stat, s);
-        }
-        // the lengths come back in both forms: the chain's are final, the open's are the datagrams'
-        if (rc == QGCM_OK &&
-            ((pk ? !pack_copy_back(*pk, s)
-                 : hipMemcpyAsync(h, r->d_arena, (size_t)cn * stride, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-             hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess))
+        const size_t span = (size_t)(c.hi - c.lo);
+        const bool up = hipMemsetAsync(sd.d_lens, 0, 4ull * c.cn, p.s) == hipSuccess &&
+                        (!span || hipMemcpyAsync(d_packed, h_packed + c.lo, span, hipMemcpyHostToDevice, p.s) == hipSuccess) &&
+                        hipMemcpyAsync(d_bufs, h_bufs, 16ull * nb, hipMemcpyHostToDevice, p.s) == hipSuccess;
+        if (!up) {
             rc = QGCM_E_HIP;
-        if (hipStreamSynchronize(s) != hipSuccess) rc = QGCM_E_HIP;
-        if (rc != QGCM_OK) return rc;
-        if (pk) pack_rebase(*pk, c0, cn);
-        for (uint32_t i = 0; i < cn; ++i) {
-            const bool ok = r->h_stat[i] == 1;
-            if (!chain) h_lens[c0 + i] = ok ? h_lens[c0 + i] - 4 - QGCM_OVERHEAD : 0;
-            if (h_status) h_status[c0 + i] = ok ? 1 : 0;
-            dropped += !ok;
+        } else if (r->gro_fused) {
+            rc = gro_resolve(ctx, d_packed, span, d_bufs, nb, c.cn, r->d_arena, stride, sd.d_lens, sd.d_peer, sd.d_descs, p.s);
+        } else {
+            rc = hip_rc(launch_gro_unpack(d_packed, span, d_bufs, nb, c.cn, r->d_arena, stride, sd.d_lens, p.s));
+            if (rc == QGCM_OK) rc = resolve(ctx, false, r->d_arena, stride, c.cn, sd.d_lens, sd.d_peer, sd.d_descs, p.s);
         }
+        rc = chunk_tail(job, sd, rc, c.c0, c.cn, nullptr, pk ? nullptr : h_arena + (uint64_t)c.c0 * stride);
+        if (rc != QGCM_OK) return rc;
     }
-    return dropped;
+    return job.dropped;
 }
 
-// Outgoing.pipeline for a batch that was read packed (qgcm_tun_read_packed): run_route_host's packed outgoing
-// chain (`tk`) with the copy-in replaced.  Frame i is slot i, so the chunks are run_route_host's; per chunk the
-// packed bytes its frames span (the table ascends: from the first frame's off to the last frame's end) and their
-// table entries (rebased to the span) go up, frames_resolve_kernel puts them into the device arena and resolves
-// them, and chain, plan, train pack, accounting and the copy back follow as in run_route_host.
+// The batch read packed (qgcm_tun_read_packed), the packed outgoing chain only.  Frame i is slot i, so the chunks
+// are run_route_host's.  Per chunk the packed bytes its frames span (the table ascends: from the first frame's off
+// to the last frame's end) and their table entries (rebased to the span) go up, and frames_resolve_kernel puts
+// them into the device arena and resolves them.
 int run_route_frames_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_frame *frames, uint64_t stride,
                           uint32_t n, uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins, uint32_t *h_peer,
                           uint8_t *h_status, TrainOut &tk) {
     if (!ctx) return QGCM_E_ARG;
-    RouteState *r = ctx_route(ctx);
     if ((stride & 3) || stride < 8 || n > QGCM_MAX_BATCH || !h_nonces || (plugins & ~kAllPlugins)) return QGCM_E_ARG;
     if (n && (!h_packed || !frames || !h_lens || !h_peer)) return QGCM_E_ARG;
     if (!frames_table_ascends(frames, n, packed_len)) return QGCM_E_ARG;
-    {
-        std::lock_guard<std::mutex> g(r->mu);
-        if (!r->set) return QGCM_E_ARG;
-    }
-    if (n == 0) return 0;
+    Pipe p;
+    int rc = pipe_enter(ctx, stride, n, p);
+    if (rc != QGCM_OK || n == 0) return rc;
+    RouteState *r = ctx_route(ctx);
     const bool gen = h_nonces == QGCM_NONCES_GENERATE;
-    std::lock_guard<std::mutex> pg(r->pipe_mu);
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
-    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
-        r->stream = nullptr;
-        return QGCM_E_HIP;
-    }
-    hipStream_t s = r->stream;
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(kRouteChunk, n),
-                                                        std::max<uint64_t>(1, kRouteChunkBytes / stride));
+    const uint32_t chunk = std::min(p.limit, n);
     // the longest span of a chunk's frames
     uint64_t max_span = 0;
     for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
         const qgcm_frame &last = frames[c0 + std::min(chunk, n - c0) - 1];
         max_span = std::max<uint64_t>(max_span, (uint64_t)last.off + last.len - frames[c0].off);
     }
-    // side buffer of a chunk as in run_route_host; the table (16-B aligned) and the packed bytes (16-B aligned,
-    // rounded up to 16 B) in a staging area of their own
-    const size_t o_desc = 0, o_lens = o_desc + 16ull * chunk, o_peer = o_lens + 4ull * chunk, o_non = o_peer + 4ull * chunk,
-                 o_stat = o_non + 12ull * chunk, o_bytes = (o_stat + chunk + 15) & ~(size_t)15,
-                 o_work = o_bytes + 4 * (size_t)chain_work_lanes(chunk), side = o_work + QGCM_CHAIN_WORK(chunk);
-    const size_t o_packed = (8ull * chunk + 15) & ~(size_t)15, staging = o_packed + (size_t)((max_span + 15) & ~(uint64_t)15);
-    if (!grow(r->d_arena, r->arena_cap, (size_t)chunk * stride) || !grow(r->d_side, r->side_cap, side) ||
-        !grow(r->d_frames, r->frames_cap, std::max<size_t>(staging, 16)) || !train_grow(r, tk, chunk, stride))
+    Side sd;
+    qgcm_frame *h_frames, *d_frames;
+    uint8_t *d_packed;
+    if (!chunk_grow(r, sd, chunk, stride, true, nullptr, &tk) || !stage_grow(r, chunk, max_span, h_frames, d_frames, d_packed))
         return QGCM_E_NOMEM;
-    r->h_stat.resize(chunk);
-    r->h_frames.resize(chunk);
-    qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
-    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
-    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
-    uint8_t *d_non = r->d_side + o_non, *d_stat = r->d_side + o_stat;
-    uint32_t *d_bytes = reinterpret_cast<uint32_t *>(r->d_side + o_bytes);
-    qgcm_frame *d_frames = reinterpret_cast<qgcm_frame *>(r->d_frames);
-    uint8_t *d_packed = r->d_frames + o_packed;
-    int dropped = 0;
+    Job job{ctx, p.s, true, true, plugins, stride, h_lens, h_peer, h_status, true, nullptr, &tk};
     for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
         const uint32_t cn = std::min(chunk, n - c0);
         const uint64_t lo = frames[c0].off, hi = (uint64_t)frames[c0 + cn - 1].off + frames[c0 + cn - 1].len;
-        for (uint32_t j = 0; j < cn; ++j) r->h_frames[j] = qgcm_frame{(uint32_t)(frames[c0 + j].off - lo), frames[c0 + j].len};
-        int rc = QGCM_OK;
-        if ((hi > lo && hipMemcpyAsync(d_packed, h_packed + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, s) != hipSuccess) ||
-            hipMemcpyAsync(d_frames, r->h_frames.data(), 8ull * cn, hipMemcpyHostToDevice, s) != hipSuccess ||
-            (!gen && hipMemcpyAsync(d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, s) != hipSuccess))
-            rc = QGCM_E_HIP;
-        if (rc == QGCM_OK)
-            rc = frames_resolve(ctx, d_packed, hi - lo, d_frames, cn, r->d_arena, stride, d_lens, d_peer, d_descs, s);
-        if (rc == QGCM_OK)
-            rc = run_chain(ctx, true, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, gen ? QGCM_NONCES_GENERATE : d_non,
-                           d_stat, d_bytes, r->d_side + o_work, s);
-        if (rc == QGCM_OK) rc = train_chunk(tk, ctx_max_keys(ctx), r->d_arena, stride, c0, cn, d_lens, d_peer, s);
-        if (rc == QGCM_OK) rc = account(ctx, QGCM_TX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
-        if (rc == QGCM_OK &&
-            (!train_copy_back(tk, s) || hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess))
-            rc = QGCM_E_HIP;
-        // every way out waits for the stream: the next call reuses the staging, and the caller its arrays
-        if (hipStreamSynchronize(s) != hipSuccess && rc == QGCM_OK) rc = QGCM_E_HIP;
+        for (uint32_t j = 0; j < cn; ++j) h_frames[j] = qgcm_frame{(uint32_t)(frames[c0 + j].off - lo), frames[c0 + j].len};
+        const bool up = (hi == lo || hipMemcpyAsync(d_packed, h_packed + lo, (size_t)(hi - lo), hipMemcpyHostToDevice, p.s) == hipSuccess) &&
+                        hipMemcpyAsync(d_frames, h_frames, 8ull * cn, hipMemcpyHostToDevice, p.s) == hipSuccess &&
+                        (gen || hipMemcpyAsync(sd.d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, p.s) == hipSuccess);
+        rc = up ? frames_resolve(ctx, d_packed, hi - lo, d_frames, cn, r->d_arena, stride, sd.d_lens, sd.d_peer, sd.d_descs, p.s)
+                : QGCM_E_HIP;
+        rc = chunk_tail(job, sd, rc, c0, cn, gen ? QGCM_NONCES_GENERATE : sd.d_non, nullptr);
         if (rc != QGCM_OK) return rc;
-        train_rebase(tk, c0, cn);
-        for (uint32_t i = 0; i < cn; ++i) {
-            const bool ok = r->h_stat[i] == 1;
-            if (h_status) h_status[c0 + i] = ok ? 1 : 0;
-            dropped += !ok;
-        }
     }
-    return dropped;
+    return job.dropped;
 }
 
-// Outgoing.pipeline for a batch that was read as super-frames (qgcm_tun_read_gso): run_route_frames_host with
-// gso_resolve_kernel in place of frames_resolve_kernel.  An entry names a run of slots, so chunks end at entry
-// boundaries, as run_route_gro_host's: entries [e0, e1), slots [c0, c0 + cn), packed bytes [lo, hi) -- every entry
-// is valid (the table is checked), so lo, a 16-B boundary, is the least off and hi the greatest end.  Per chunk
-// the span and the entries, rebased to the span and to the chunk's first slot, go up; chain, plan, train pack,
-// accounting and the copy back follow as in run_route_frames_host.
+// The batch read as super-frames (qgcm_tun_read_gso), the packed outgoing chain only.  An entry names a run of
+// slots, so chunks end at entry boundaries; every entry is valid (the table is checked), so lo, a 16-B boundary, is
+// the least off and hi the greatest end.  Per chunk the span and the entries (rebased to the span and to the
+// chunk's first slot) go up, and gso_resolve_kernel segments them into the device arena and resolves them.
 int run_route_gso_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint64_t packed_len, const qgcm_gso_frame *frames, uint32_t n_frames,
                        uint64_t stride, uint32_t n, uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins, uint32_t *h_peer,
                        uint8_t *h_status, TrainOut &tk) {
     if (!ctx) return QGCM_E_ARG;
-    RouteState *r = ctx_route(ctx);
     if ((stride & 3) || stride < 8 || n > QGCM_MAX_BATCH || n_frames > n || !h_nonces || (plugins & ~kAllPlugins)) return QGCM_E_ARG;
     if (n && (!h_packed || !frames || !h_lens || !h_peer)) return QGCM_E_ARG;
     if (!gso_table_ok(frames, n_frames, n, packed_len)) return QGCM_E_ARG;
-    {
-        std::lock_guard<std::mutex> g(r->mu);
-        if (!r->set) return QGCM_E_ARG;
-    }
-    if (n == 0) return 0;
+    Pipe p;
+    int rc = pipe_enter(ctx, stride, n, p);
+    if (rc != QGCM_OK || n == 0) return rc;
+    RouteState *r = ctx_route(ctx);
     const bool gen = h_nonces == QGCM_NONCES_GENERATE;
-    std::lock_guard<std::mutex> pg(r->pipe_mu);
-    if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
-    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
-        r->stream = nullptr;
-        return QGCM_E_HIP;
-    }
-    hipStream_t s = r->stream;
-    const uint32_t limit = (uint32_t)std::min<uint64_t>(kRouteChunk, std::max<uint64_t>(1, kRouteChunkBytes / stride));
-    struct Chunk {
-        uint32_t e0, e1, c0, cn;
-        uint64_t lo, hi;
-    };
-    std::vector<Chunk> chunks;
-    uint32_t max_cn = 0, max_ne = 0;
-    uint64_t max_span = 0;
+    Chunks chunks;
     for (uint32_t e = 0; e < n_frames;) {
         Chunk c{e, e, frames[e].first, 0, UINT64_MAX, 0};
         for (; e < n_frames; ++e) {
-            if (c.cn && (uint64_t)c.cn + frames[e].count > limit) break;
+            if (c.cn && (uint64_t)c.cn + frames[e].count > p.limit) break;
             c.cn += frames[e].count;
             c.lo = std::min<uint64_t>(c.lo, frames[e].off);
             c.hi = std::max<uint64_t>(c.hi, (uint64_t)frames[e].off + frames[e].len);
         }
         c.e1 = e;
-        max_cn = std::max(max_cn, c.cn);
-        max_ne = std::max(max_ne, c.e1 - c.e0);
-        max_span = std::max(max_span, c.hi - c.lo);
-        chunks.push_back(c);
+        chunks.add(c);
     }
-    // side buffer of a chunk as in run_route_frames_host; the table (16-B aligned) and the packed bytes (16-B
-    // aligned, rounded up to 16 B) in a staging area of their own
-    const size_t o_desc = 0, o_lens = o_desc + 16ull * max_cn, o_peer = o_lens + 4ull * max_cn, o_non = o_peer + 4ull * max_cn,
-                 o_stat = o_non + 12ull * max_cn, o_bytes = (o_stat + max_cn + 15) & ~(size_t)15,
-                 o_work = o_bytes + 4 * (size_t)chain_work_lanes(max_cn), side = o_work + QGCM_CHAIN_WORK(max_cn);
-    const size_t o_packed = 32ull * max_ne, staging = o_packed + (size_t)((max_span + 15) & ~(uint64_t)15);
-    if (!grow(r->d_arena, r->arena_cap, (size_t)max_cn * stride) || !grow(r->d_side, r->side_cap, side) ||
-        !grow(r->d_gso, r->gso_cap, std::max<size_t>(staging, 16)) || !train_grow(r, tk, max_cn, stride))
+    Side sd;
+    qgcm_gso_frame *h_frames, *d_frames;
+    uint8_t *d_packed;
+    if (!chunk_grow(r, sd, chunks.max_cn, stride, true, nullptr, &tk) ||
+        !stage_grow(r, chunks.max_entries, chunks.max_span, h_frames, d_frames, d_packed))
         return QGCM_E_NOMEM;
-    r->h_stat.resize(max_cn);
-    r->h_gso.resize(max_ne);
-    qgcm_desc *d_descs = reinterpret_cast<qgcm_desc *>(r->d_side + o_desc);
-    uint32_t *d_lens = reinterpret_cast<uint32_t *>(r->d_side + o_lens);
-    uint32_t *d_peer = reinterpret_cast<uint32_t *>(r->d_side + o_peer);
-    uint8_t *d_non = r->d_side + o_non, *d_stat = r->d_side + o_stat;
-    uint32_t *d_bytes = reinterpret_cast<uint32_t *>(r->d_side + o_bytes);
-    qgcm_gso_frame *d_frames = reinterpret_cast<qgcm_gso_frame *>(r->d_gso);
-    uint8_t *d_packed = r->d_gso + o_packed;
-    int dropped = 0;
-    for (const Chunk &c : chunks) {
-        const uint32_t ne = c.e1 - c.e0, cn = c.cn, c0 = c.c0;
+    Job job{ctx, p.s, true, true, plugins, stride, h_lens, h_peer, h_status, true, nullptr, &tk};
+    for (const Chunk &c : chunks.v) {
+        const uint32_t ne = c.e1 - c.e0;
         for (uint32_t j = 0; j < ne; ++j) {
-            r->h_gso[j] = frames[c.e0 + j];
-            r->h_gso[j].off -= (uint32_t)c.lo;
-            r->h_gso[j].first -= c0;
+            h_frames[j] = frames[c.e0 + j];
+            h_frames[j].off -= (uint32_t)c.lo;
+            h_frames[j].first -= c.c0;
         }
-        int rc = QGCM_OK;
-        if ((c.hi > c.lo && hipMemcpyAsync(d_packed, h_packed + c.lo, (size_t)(c.hi - c.lo), hipMemcpyHostToDevice, s) != hipSuccess) ||
-            hipMemcpyAsync(d_frames, r->h_gso.data(), 32ull * ne, hipMemcpyHostToDevice, s) != hipSuccess ||
-            (!gen && hipMemcpyAsync(d_non, h_nonces + 12ull * c0, 12ull * cn, hipMemcpyHostToDevice, s) != hipSuccess))
-            rc = QGCM_E_HIP;
-        if (rc == QGCM_OK)
-            rc = gso_resolve(ctx, d_packed, c.hi - c.lo, d_frames, ne, cn, r->d_arena, stride, d_lens, d_peer, d_descs, s);
-        if (rc == QGCM_OK)
-            rc = run_chain(ctx, true, r->d_arena, stride, cn, d_lens, d_peer, d_descs, plugins, gen ? QGCM_NONCES_GENERATE : d_non,
-                           d_stat, d_bytes, r->d_side + o_work, s);
-        if (rc == QGCM_OK) rc = train_chunk(tk, ctx_max_keys(ctx), r->d_arena, stride, c0, cn, d_lens, d_peer, s);
-        if (rc == QGCM_OK) rc = account(ctx, QGCM_TX, cn, d_peer, nullptr, d_bytes, true, d_stat, s);
-        if (rc == QGCM_OK &&
-            (!train_copy_back(tk, s) || hipMemcpyAsync(h_peer + c0, d_peer, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(r->h_stat.data(), d_stat, cn, hipMemcpyDeviceToHost, s) != hipSuccess ||
-             hipMemcpyAsync(h_lens + c0, d_lens, 4ull * cn, hipMemcpyDeviceToHost, s) != hipSuccess))
-            rc = QGCM_E_HIP;
-        // every way out waits for the stream: the next call reuses the staging, and the caller its arrays
-        if (hipStreamSynchronize(s) != hipSuccess && rc == QGCM_OK) rc = QGCM_E_HIP;
+        const size_t span = (size_t)(c.hi - c.lo);
+        const bool up = (!span || hipMemcpyAsync(d_packed, h_packed + c.lo, span, hipMemcpyHostToDevice, p.s) == hipSuccess) &&
+                        hipMemcpyAsync(d_frames, h_frames, 32ull * ne, hipMemcpyHostToDevice, p.s) == hipSuccess &&
+                        (gen || hipMemcpyAsync(sd.d_non, h_nonces + 12ull * c.c0, 12ull * c.cn, hipMemcpyHostToDevice, p.s) == hipSuccess);
+        rc = up ? gso_resolve(ctx, d_packed, span, d_frames, ne, c.cn, r->d_arena, stride, sd.d_lens, sd.d_peer, sd.d_descs, p.s)
+                : QGCM_E_HIP;
+        rc = chunk_tail(job, sd, rc, c.c0, c.cn, gen ? QGCM_NONCES_GENERATE : sd.d_non, nullptr);
         if (rc != QGCM_OK) return rc;
-        train_rebase(tk, c0, cn);
-        for (uint32_t i = 0; i < cn; ++i) {
-            const bool ok = r->h_stat[i] == 1;
-            if (h_status) h_status[c0 + i] = ok ? 1 : 0;
-            dropped += !ok;
-        }
     }
-    return dropped;
+    return job.dropped;
 }
 
 }  // namespace
@@ -1136,11 +1088,8 @@ int qgcm_send_plan_host(qgcm_ctx *ctx, uint32_t n, const uint32_t *h_lens, const
         return QGCM_OK;
     }
     if (hipSetDevice(ctx_device(ctx)) != hipSuccess) return QGCM_E_HIP;
-    if (!r->stream && hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) != hipSuccess) {
-        r->stream = nullptr;
-        return QGCM_E_HIP;
-    }
-    hipStream_t s = r->stream;
+    hipStream_t s = pipe_stream(r);
+    if (!s) return QGCM_E_HIP;
     // trains (16-B aligned), lengths, peers, order, counts, then the work area (256-B aligned)
     const size_t o_trains = 0, o_lens = o_trains + 16ull * n, o_peer = o_lens + 4ull * n, o_order = o_peer + 4ull * n,
                  o_counts = o_order + 4ull * n, o_work = (o_counts + 8 + 255) & ~(size_t)255;
@@ -1223,9 +1172,8 @@ int qgcm_deliver_pack(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride, ui
 int qgcm_route_chain_open_packed_host(qgcm_ctx *ctx, const uint8_t *h_arena, uint64_t stride, uint32_t n,
                                       uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
                                       uint8_t *h_out, uint64_t out_cap, qgcm_pack_rec *h_recs, uint64_t out[3]) {
-    if (!out || (n && (!h_out || !h_recs))) return QGCM_E_ARG;
-    out[0] = out[1] = out[2] = 0;
-    PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), h_recs, out};
+    PackOut pk;
+    if (!pack_out(pk, false, n, h_out, out_cap, h_recs, out)) return QGCM_E_ARG;
     // the arena is only read: with `pk` the copy back never names it
     return run_route_host(ctx, false, const_cast<uint8_t *>(h_arena), stride, n, h_lens, nullptr, h_peer, h_status, true,
                           plugins, &pk);
@@ -1235,9 +1183,8 @@ int qgcm_route_chain_open_gro_packed_host(qgcm_ctx *ctx, const uint8_t *h_packed
                                           const qgcm_gro_buf *bufs, uint32_t n_bufs, uint64_t stride, uint32_t n,
                                           uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
                                           uint8_t *h_out, uint64_t out_cap, qgcm_pack_rec *h_recs, uint64_t out[3]) {
-    if (!out || (n && (!h_out || !h_recs))) return QGCM_E_ARG;
-    out[0] = out[1] = out[2] = 0;
-    PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), h_recs, out};
+    PackOut pk;
+    if (!pack_out(pk, false, n, h_out, out_cap, h_recs, out)) return QGCM_E_ARG;
     return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, nullptr, stride, n, h_lens, h_peer, h_status, true,
                               plugins, &pk);
 }
@@ -1260,10 +1207,8 @@ int qgcm_deliver_coalesce(qgcm_ctx *ctx, const uint8_t *d_arena, uint64_t stride
 int qgcm_route_chain_open_coalesced_host(qgcm_ctx *ctx, const uint8_t *h_arena, uint64_t stride, uint32_t n,
                                          uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
                                          uint8_t *h_out, uint64_t out_cap, qgcm_gso_frame *h_frames, uint64_t out[5]) {
-    if (!out || (n && (!h_out || !h_frames))) return QGCM_E_ARG;
-    out[0] = out[1] = out[2] = out[3] = out[4] = 0;
-    PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), nullptr, out};
-    pk.h_frames = h_frames;
+    PackOut pk;
+    if (!pack_out(pk, true, n, h_out, out_cap, h_frames, out)) return QGCM_E_ARG;
     return run_route_host(ctx, false, const_cast<uint8_t *>(h_arena), stride, n, h_lens, nullptr, h_peer, h_status, true,
                           plugins, &pk);
 }
@@ -1273,10 +1218,8 @@ int qgcm_route_chain_open_gro_coalesced_host(qgcm_ctx *ctx, const uint8_t *h_pac
                                              uint32_t *h_lens, uint32_t plugins, uint32_t *h_peer, uint8_t *h_status,
                                              uint8_t *h_out, uint64_t out_cap, qgcm_gso_frame *h_frames,
                                              uint64_t out[5]) {
-    if (!out || (n && (!h_out || !h_frames))) return QGCM_E_ARG;
-    out[0] = out[1] = out[2] = out[3] = out[4] = 0;
-    PackOut pk{h_out, std::min<uint64_t>(out_cap, kPackMaxCap), nullptr, out};
-    pk.h_frames = h_frames;
+    PackOut pk;
+    if (!pack_out(pk, true, n, h_out, out_cap, h_frames, out)) return QGCM_E_ARG;
     return run_route_gro_host(ctx, h_packed, packed_len, bufs, n_bufs, nullptr, stride, n, h_lens, h_peer, h_status, true,
                               plugins, &pk);
 }
@@ -1302,10 +1245,8 @@ int qgcm_route_chain_seal_packed_host(qgcm_ctx *ctx, const uint8_t *h_arena, uin
                                       const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
                                       uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order,
                                       uint64_t out[4]) {
-    if (!out || (n && (!h_out || !h_ptrains))) return QGCM_E_ARG;
-    out[0] = out[1] = out[2] = out[3] = 0;
-    TrainOut tk{h_out, std::min<uint64_t>(out_cap, kTrainMaxCap), h_ptrains, h_order, out};
-    if (!plan_limits_resolve(limits, &tk.lim)) return QGCM_E_ARG;
+    TrainOut tk;
+    if (!train_out(tk, n, h_out, out_cap, h_ptrains, h_order, limits, out)) return QGCM_E_ARG;
     // the arena is only read: with `tk` the copy back never names it
     return run_route_host(ctx, true, const_cast<uint8_t *>(h_arena), stride, n, h_lens, h_nonces, h_peer, h_status, true,
                           plugins, nullptr, &tk);
@@ -1325,10 +1266,8 @@ int qgcm_route_chain_seal_frames_host(qgcm_ctx *ctx, const uint8_t *h_packed, ui
                                       uint64_t stride, uint32_t n, uint32_t *h_lens, const uint8_t *h_nonces, uint32_t plugins,
                                       const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status, uint8_t *h_out,
                                       uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order, uint64_t out[4]) {
-    if (!out || (n && (!h_out || !h_ptrains))) return QGCM_E_ARG;
-    out[0] = out[1] = out[2] = out[3] = 0;
-    TrainOut tk{h_out, std::min<uint64_t>(out_cap, kTrainMaxCap), h_ptrains, h_order, out};
-    if (!plan_limits_resolve(limits, &tk.lim)) return QGCM_E_ARG;
+    TrainOut tk;
+    if (!train_out(tk, n, h_out, out_cap, h_ptrains, h_order, limits, out)) return QGCM_E_ARG;
     return run_route_frames_host(ctx, h_packed, packed_len, frames, stride, n, h_lens, h_nonces, plugins, h_peer, h_status, tk);
 }
 
@@ -1348,10 +1287,8 @@ int qgcm_route_chain_seal_gso_host(qgcm_ctx *ctx, const uint8_t *h_packed, uint6
                                    uint32_t n_frames, uint64_t stride, uint32_t n, uint32_t *h_lens, const uint8_t *h_nonces,
                                    uint32_t plugins, const qgcm_plan_limits *limits, uint32_t *h_peer, uint8_t *h_status,
                                    uint8_t *h_out, uint64_t out_cap, qgcm_ptrain *h_ptrains, uint32_t *h_order, uint64_t out[4]) {
-    if (!out || (n && (!h_out || !h_ptrains))) return QGCM_E_ARG;
-    out[0] = out[1] = out[2] = out[3] = 0;
-    TrainOut tk{h_out, std::min<uint64_t>(out_cap, kTrainMaxCap), h_ptrains, h_order, out};
-    if (!plan_limits_resolve(limits, &tk.lim)) return QGCM_E_ARG;
+    TrainOut tk;
+    if (!train_out(tk, n, h_out, out_cap, h_ptrains, h_order, limits, out)) return QGCM_E_ARG;
     return run_route_gso_host(ctx, h_packed, packed_len, frames, n_frames, stride, n, h_lens, h_nonces, plugins, h_peer, h_status, tk);
 }
 
