@@ -360,6 +360,25 @@ def test_round_trip(cx, sessions, n, stride):
         assert np.array_equal(o_arena[i, :lens[i]], arena[i, :lens[i]])
 
 
+def test_round_trip_every_length_to_130(cx):
+    """Lengths 1..130 once each over three sessions, sealed, then opened under the mirrored sessions: every
+    L mod 64 twice -- the lane that owns the partial block, the lane that computes E_K(J0), the words of the
+    partial block and the shifts of dtls_write_tag in every combination (the other tests reach 49..63,
+    65..79 and so on only through four long records)."""
+    rng = np.random.default_rng(0xD7150E00)
+    tx = M.make_sessions(3, 0xD715E)
+    rx = M.mirror(tx)
+    install(cx, tx)
+    install(cx, rx, first=64)
+    arena, lens, peer, hdr = plain_batch(rng, 130, SHORT, list(range(1, 131)), 3)
+    s_arena, s_lens, s_hdr, s_status, _ = check(cx, True, tx, arena, lens, peer, hdr, what="seal")
+    assert s_status.all()
+    o_arena, o_lens, _, o_status, _ = check(cx, False, rx, s_arena, s_lens, peer, s_hdr, first=64, what="open")
+    assert o_status.all() and o_lens.tolist() == lens.tolist()
+    for i in range(130):
+        assert np.array_equal(o_arena[i, :lens[i]], arena[i, :lens[i]])
+
+
 def test_existing_batch_calls_unaffected(cx):
     """After DTLS traffic a keyed qgcm_seal_batch / qgcm_open_batch on other key slots gives the oracle's bytes."""
     import torch

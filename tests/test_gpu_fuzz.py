@@ -125,7 +125,8 @@ def test_descriptor_fuzz_vs_oracle(torch, fuzz_ctxs, fuzz_keys, variant, seed, s
     assert np.array_equal(st, valid.astype(np.uint8)), f"seal status: {int((st != valid).sum())} packets differ"
     got = arena.cpu().numpy()
     if not np.array_equal(got, ref):
-        bad = [int(i) for i in range(n) if not np.array_equal(got[offs[i]:offs[i] + slot[i]], ref[offs[i]:offs[i] + slot[i]])]
+        ends = offs.astype(np.int64) + slot  # (uint64 + int64 is a float in numpy: not a slice index)
+        bad = [i for i in range(n) if not np.array_equal(got[int(offs[i]):int(ends[i])], ref[int(offs[i]):int(ends[i])])]
         pytest.fail(f"seed {seed}: {len(bad)} of {n} slots differ, first {bad[:5]} keys {kidx[bad[:5]].tolist()} "
                     f"lengths {lens[bad[:5]].tolist()}")
 
