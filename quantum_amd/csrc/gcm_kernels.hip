@@ -502,32 +502,14 @@ __device__ __forceinline__ uint32_t load_bytes(const uint8_t *p, uint32_t nbytes
     return v;
 }
 
-// Reads the 28-byte tag||nonce that starts at byte L of data (any alignment; data 4-aligned).
-// Out: tn[0..3] = tag words, tn[4..6] = nonce words (LE), and the s = L%4 bytes before it.
 // NOTE: the packet kernels address LDS absolutely from 0, so they must own NO static LDS: the
 // build passes -disable-promote-alloca-to-lds, tail values are plain scalars (no private arrays
 // or structs left for the compiler to spill), and init_kernels() refuses a kernel whose static
 // LDS size is not 0.
 
-// Reads the 28-byte tag||nonce that starts at byte L of data (any alignment; data 4-aligned):
-// tag words g0..g3, nonce words n0..n2 (LE), and the s = L%4 payload bytes before it (prefix).
-__device__ __forceinline__ void read_tail(const uint8_t *data, uint32_t L, uint32_t &g0, uint32_t &g1, uint32_t &g2,
-                                          uint32_t &g3, uint32_t &n0, uint32_t &n1, uint32_t &n2) {
-    const uint32_t s = L & 3u;
-    const uint32_t *t = reinterpret_cast<const uint32_t *>(data + (L & ~3u));
-    const uint32_t w0 = t[0], w1 = t[1], w2 = t[2], w3 = t[3], w4 = t[4], w5 = t[5], w6 = t[6];
-    const uint32_t w7 = load_bytes(data + (L & ~3u) + 28, s);
-    g0 = __builtin_amdgcn_alignbyte(w1, w0, s);
-    g1 = __builtin_amdgcn_alignbyte(w2, w1, s);
-    g2 = __builtin_amdgcn_alignbyte(w3, w2, s);
-    g3 = __builtin_amdgcn_alignbyte(w4, w3, s);
-    n0 = __builtin_amdgcn_alignbyte(w5, w4, s);
-    n1 = __builtin_amdgcn_alignbyte(w6, w5, s);
-    n2 = __builtin_amdgcn_alignbyte(w7, w6, s);
-}
-
-// The two halves of read_tail: the quad kernel reads the nonce when the packet starts and the
-// received tag only when it compares it (4 fewer VGPRs live across the block loop).
+// The 28-byte tag||nonce that starts at byte L of data (any alignment; data 4-aligned) is read in two
+// halves, nonce words n0..n2 (LE) and tag words g0..g3: the quad kernel reads the nonce when the packet
+// starts and the received tag only when it compares it (4 fewer VGPRs live across the block loop).
 __device__ __forceinline__ void read_nonce(const uint8_t *data, uint32_t L, uint32_t &n0, uint32_t &n1, uint32_t &n2) {
     const uint32_t s = L & 3u;
     const uint32_t *t = reinterpret_cast<const uint32_t *>(data + (L & ~3u));
@@ -584,30 +566,59 @@ __device__ __forceinline__ uint32_t quad_xor(uint32_t v) {
     return v;
 }
 
+// A frame tells quad_packet where a packet's pieces lie: where the data begins, where the nonce comes from,
+// the additional-data block of lane 3 and its length, how the tag is written and read, and whether b.status
+// may be NULL.  Passed by const reference and inlined whole; everything else of quad_packet is shared.
+// TunnelFrame, the tunnel's own packets: Raw[0:4] | data | tag | nonce.  The nonce is the batch's array's or
+// read from the tail, the additional data is Raw[0:aad_len] (at most 4 bytes here), and the tail is written
+// as one run of tag||nonce.
+struct TunnelFrame {
+    static constexpr bool kStatusAlways = false;
+    __device__ __forceinline__ uint8_t *data(uint8_t *raw) const { return raw + 4; }  // common.PacketStart
+    template <bool kSeal>
+    __device__ __forceinline__ void nonce(const Batch &b, uint32_t pkt, const uint8_t *data, uint32_t L, uint32_t &n0,
+                                          uint32_t &n1, uint32_t &n2) const {
+        if (kSeal && b.nonces) {
+            const uint32_t *np = reinterpret_cast<const uint32_t *>(b.nonces + 12ull * pkt);
+            n0 = np[0];
+            n1 = np[1];
+            n2 = np[2];
+        } else {
+            read_nonce(data, L, n0, n1, n2);
+        }
+    }
+    __device__ __forceinline__ void aad_block(const Batch &b, const uint8_t *raw, uint32_t, uint32_t &z0, uint32_t &,
+                                              uint32_t &, uint32_t &) const {
+        if (b.aad_len)
+            z0 = *reinterpret_cast<const uint32_t *>(raw) & (b.aad_len >= 4 ? 0xffffffffu : lowmask(b.aad_len));
+    }
+    __device__ __forceinline__ uint32_t aad_len(const Batch &b) const { return b.aad_len; }
+    __device__ __forceinline__ void put_tag(uint8_t *data, uint32_t L, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3,
+                                            uint32_t n0, uint32_t n1, uint32_t n2, uint32_t prefix) const {
+        write_tail(data, L, t0, t1, t2, t3, n0, n1, n2, prefix);
+    }
+    __device__ __forceinline__ void get_tag(const uint8_t *data, uint32_t L, uint32_t &g0, uint32_t &g1, uint32_t &g2,
+                                            uint32_t &g3) const {
+        read_tag(data, L, g0, g1, g2, g3);
+    }
+};
+
 // One packet of a quad tile (4 lanes, lane m owns blocks b = m mod 4): CTR + GHASH + tag, in place.
-template <bool kSeal, class Eng>
+template <bool kSeal, class Eng, class Frame = TunnelFrame>
 __device__ __forceinline__ void quad_packet(const Batch &b, const Eng &eng, uint32_t pkt, uint64_t off, uint32_t L,
-                                            uint32_t wkey, uint32_t m, uint32_t gH4) {
+                                            uint32_t wkey, uint32_t m, uint32_t gH4, const Frame &f = Frame{}) {
     const uint4 *Hg = b.gh_table + (size_t)wkey * kGhEntries;  // comb tables of H^k (global)
     uint8_t *raw = b.arena + off;
-    uint8_t *data = raw + 4;  // common.PacketStart
+    uint8_t *data = f.data(raw);
 
-    uint32_t g0 = 0, g1 = 0, g2 = 0, g3 = 0, n0, n1, n2;
-    if (kSeal && b.nonces) {
-        const uint32_t *np = reinterpret_cast<const uint32_t *>(b.nonces + 12ull * pkt);
-        n0 = np[0];
-        n1 = np[1];
-        n2 = np[2];
-    } else {
-        read_nonce(data, L, n0, n1, n2);
-    }
+    uint32_t n0, n1, n2;
+    f.template nonce<kSeal>(b, pkt, data, L, n0, n1, n2);
     const uint32_t nfull = L >> 4, r = L & 15u;
     const uint32_t d = nfull + (r ? 1u : 0u);  // data blocks incl. the partial one
 
     // lane 3 starts its chain with the additional data block (block -1)
     uint32_t z0 = 0, z1 = 0, z2 = 0, z3 = 0;
-    if (m == 3 && b.aad_len)
-        z0 = *reinterpret_cast<const uint32_t *>(raw) & (b.aad_len >= 4 ? 0xffffffffu : lowmask(b.aad_len));
+    if (m == 3) f.aad_block(b, raw, L, z0, z1, z2, z3);
     int blast = -1;
 
     uint32_t e0 = 0, e1 = 0, e2 = 0, e3 = 0;  // E_K(J0)
@@ -650,7 +661,8 @@ __device__ __forceinline__ void quad_packet(const Batch &b, const Eng &eng, uint
         eng.block(cc, ctr & 0xffu, k0, k1, k2, k3);
         if (part) {
             uint8_t *blk = data + 16u * nfull;
-            const W4 in = *reinterpret_cast<const W4 *>(blk);  // reads into tag area: inside the slot
+            // reads into the tag area (a seal: the 16 bytes the tag will take): below L + 16, inside the slot
+            const W4 in = *reinterpret_cast<const W4 *>(blk);
             const uint32_t q = r >> 2, sb = r & 3u;
             const uint32_t o0 = in.x ^ k0, o1 = in.y ^ k1, o2 = in.z ^ k2, o3 = in.w ^ k3;
             uint32_t *bw = reinterpret_cast<uint32_t *>(blk);
@@ -660,7 +672,7 @@ __device__ __forceinline__ void quad_packet(const Batch &b, const Eng &eng, uint
             const uint32_t oq = sel4(q, o0, o1, o2, o3) & lowmask(sb);
             W4 c = kSeal ? W4{o0, o1, o2, o3} : in;
             if (kSeal)
-                prefix = oq;  // written with tag||nonce by write_tail
+                prefix = oq;  // written with the tag by the frame's put_tag
             else
                 store_bytes(blk + 4 * q, oq, sb);
             c.x &= q > 0 ? 0xffffffffu : lowmask(sb);
@@ -688,7 +700,7 @@ __device__ __forceinline__ void quad_packet(const Batch &b, const Eng &eng, uint
         const uint32_t tsel = em == 2 ? kGhH2 : em == 3 ? kGhH3 : em == 4 ? kGhH4 : kGhH5;
         ghash_mul_global(z0, z1, z2, z3, Hg + tsel);
         uint32_t l0, l1, l2, l3;
-        ghash_lenblock_global(b.aad_len, L, Hg, l0, l1, l2, l3);
+        ghash_lenblock_global(f.aad_len(b), L, Hg, l0, l1, l2, l3);
         z0 = quad_xor(z0) ^ l0;
         z1 = quad_xor(z1) ^ l1;
         z2 = quad_xor(z2) ^ l2;
@@ -703,11 +715,12 @@ __device__ __forceinline__ void quad_packet(const Batch &b, const Eng &eng, uint
     const uint32_t owner = r ? (nfull & 3u) : 0u;
     if (kSeal) {
         if (m == owner) {
-            write_tail(data, L, t0, t1, t2, t3, n0, n1, n2, prefix);
-            if (b.status) b.status[pkt] = 1;
+            f.put_tag(data, L, t0, t1, t2, t3, n0, n1, n2, prefix);
+            if (Frame::kStatusAlways || b.status) b.status[pkt] = 1;
         }
     } else {
-        read_tag(data, L, g0, g1, g2, g3);  // the tag is never written by Open
+        uint32_t g0, g1, g2, g3;
+        f.get_tag(data, L, g0, g1, g2, g3);  // the tag is never written by Open
         const bool ok = ((t0 ^ g0) | (t1 ^ g1) | (t2 ^ g2) | (t3 ^ g3)) == 0;
         if (!ok) {
             // Go 1.9 crypto/cipher gcm Open: zero the would-be plaintext on tag mismatch.
@@ -721,7 +734,7 @@ __device__ __forceinline__ void quad_packet(const Batch &b, const Eng &eng, uint
                 store_bytes(data + 16u * nfull + (r & ~3u), 0, r & 3u);
             }
         }
-        if (b.status && m == 0) b.status[pkt] = ok ? 1 : 0;
+        if ((Frame::kStatusAlways || b.status) && m == 0) b.status[pkt] = ok ? 1 : 0;
     }
 }
 
@@ -761,6 +774,8 @@ template <bool kDesc>
 constexpr int quad_waves() { return kDesc ? 12 : 16; }
 template <bool kDesc>
 constexpr int quad_wpe() { return kDesc ? 3 : 8; }
+// LDS of the per-wave kernels (variant 13 and gcm_dtls_kernel): Te, then a comb per wave
+constexpr uint32_t kDescLds = kTeBytes + (uint32_t)quad_waves<true>() * kGhBytes;
 
 template <bool kSeal, bool kDesc>
 __global__ void __launch_bounds__(quad_waves<kDesc>() * 64) __attribute__((amdgpu_waves_per_eu(quad_wpe<kDesc>(),
@@ -970,12 +985,16 @@ extern "C" int qgcm_debug_quad_stats(unsigned long long *out, int n, int reset) 
 // DTLS 1.2 records (include/qgcm.h "DTLS 1.2 records on routed batches"): gcm_dtls_kernel, the per-wave
 // descriptor kernel (gcm_quad_kernel<kSeal, true>: engine Tab2, each wave's 4-bit comb of its key's H^4 in its
 // own 8 KiB of LDS, key-sorted 16-packet tiles from launch_quad_worklist handed out by the global tile
-// counter) over another frame.  dtls_packet is quad_packet's sibling: the record starts at Raw[0]; the nonce is
-// the session's IV and the explicit nonce of the packet's header entry (b[13:21]); lane 3 starts its Horner
-// chain with the 13 bytes epoch | seq | type | version | L built from the header entry, zero-padded to a block;
-// the length block counts 13 bytes of additional data; the tag is written or compared at Raw[L:] with nothing
-// behind it.  The header entry is complete before the launch (the numbering kernel of dtls_kernels.hip writes a
-// sealed record's with the sequence number it hands out), so seal and open read it alike.
+// counter) over another frame.  A record goes through quad_packet itself, with DtlsFrame in TunnelFrame's
+// place: the record starts at Raw[0]; the nonce is the session's IV and the explicit nonce of the packet's
+// header entry (b[13:21]); lane 3 starts its Horner chain with the 13 bytes epoch | seq | type | version | L
+// built from the header entry, zero-padded to a block; the length block counts 13 bytes of additional data;
+// the tag is written or compared at Raw[L:] with nothing behind it.  The header entry is complete before the
+// launch (the numbering kernel of dtls_kernels.hip writes a sealed record's with the sequence number it hands
+// out), so seal and open read it alike.  The frame costs nothing: all 19 kernels of this file compile to the
+// instruction streams they had when the record routine was a copy of quad_packet (profiles/quad_frames).
+// The tile loop still repeats gcm_quad_kernel's kDesc branch: shared helpers for it changed the per-wave
+// kernels' streams (profiles/quad_frames/tile_step.md), so it stays spelt out.
 
 // The 16-byte tag at byte L of data (any alignment; data 4-aligned), as read_tag, but no byte at or past
 // L + 16 is read: the fifth dword only when L % 4 != 0, where it holds a byte of the tag and ends inside
@@ -1005,150 +1024,41 @@ __device__ __forceinline__ void dtls_write_tag(uint8_t *data, uint32_t L, uint32
     if (s) store_bytes(data + (L & ~3u) + 16, g3 >> sh, s);
 }
 
-// One record of a quad tile (4 lanes, lane m owns blocks b = m mod 4): CTR + GHASH + tag, in place.
-// iv: the session's write (seal) or read (open) IV; hb: the packet's header entry (16-B aligned).
-template <bool kSeal, class Eng>
-__device__ __forceinline__ void dtls_packet(const Batch &b, const Eng &eng, uint32_t pkt, uint64_t off, uint32_t L,
-                                            uint32_t wkey, uint32_t m, uint32_t gH4, uint32_t iv,
-                                            const qgcm_dtls_hdr *hb) {
-    const uint4 *Hg = b.gh_table + (size_t)wkey * kGhEntries;  // comb tables of H^k (global)
-    uint8_t *data = b.arena + off;
-
-    const uint32_t *hw = reinterpret_cast<const uint32_t *>(hb);
-    const uint32_t h3 = hw[3], h4 = hw[4], h5 = hw[5];
-    const uint32_t n0 = iv;
-    const uint32_t n1 = __builtin_amdgcn_alignbyte(h4, h3, 1);  // b[13:17]
-    const uint32_t n2 = __builtin_amdgcn_alignbyte(h5, h4, 1);  // b[17:21]
-    const uint32_t nfull = L >> 4, r = L & 15u;
-    const uint32_t d = nfull + (r ? 1u : 0u);  // data blocks incl. the partial one
-
-    // lane 3 starts its chain with the additional data block (block -1):
+// quad_packet's frame for one record.  iv: the session's write (seal) or read (open) IV; hdr: the packet's
+// header entry (16-B aligned).  The record ends with its tag: no byte at or past L + 16 is touched.
+struct DtlsFrame {
+    uint32_t iv;
+    const qgcm_dtls_hdr *hdr;
+    static constexpr bool kStatusAlways = true;  // b.status is never NULL here
+    __device__ __forceinline__ const uint32_t *hw() const { return reinterpret_cast<const uint32_t *>(hdr); }
+    __device__ __forceinline__ uint8_t *data(uint8_t *raw) const { return raw; }
+    template <bool kSeal>
+    __device__ __forceinline__ void nonce(const Batch &, uint32_t, const uint8_t *, uint32_t, uint32_t &n0, uint32_t &n1,
+                                          uint32_t &n2) const {
+        const uint32_t h3 = hw()[3], h4 = hw()[4], h5 = hw()[5];
+        n0 = iv;
+        n1 = __builtin_amdgcn_alignbyte(h4, h3, 1);  // b[13:17]
+        n2 = __builtin_amdgcn_alignbyte(h5, h4, 1);  // b[17:21]
+    }
     // epoch(2) | seq(6) = b[3:11], type | version = b[0:3], L big endian, three zero bytes
-    uint32_t z0 = 0, z1 = 0, z2 = 0, z3 = 0;
-    if (m == 3) {
-        const uint32_t h0 = hw[0], h1 = hw[1], h2 = hw[2];
+    __device__ __forceinline__ void aad_block(const Batch &, const uint8_t *, uint32_t L, uint32_t &z0, uint32_t &z1,
+                                              uint32_t &z2, uint32_t &z3) const {
+        const uint32_t h0 = hw()[0], h1 = hw()[1], h2 = hw()[2];
         z0 = __builtin_amdgcn_alignbyte(h1, h0, 3);
         z1 = __builtin_amdgcn_alignbyte(h2, h1, 3);
         z2 = (h0 & 0x00ffffffu) | ((L >> 8) << 24);
         z3 = L & 0xffu;
     }
-    int blast = -1;
-
-    uint32_t e0 = 0, e1 = 0, e2 = 0, e3 = 0;  // E_K(J0)
-    uint32_t prefix = 0;
-    {
-    Ctr cc;
-    uint32_t hi = 0;
-    eng.setup(cc, n0, n1, n2, 0);
-    for (uint32_t bi = m; bi < nfull; bi += 4) {
-        const uint32_t ctr = bi + 2;  // inc32(J0) + bi
-        if ((ctr >> 8) != hi) {
-            hi = ctr >> 8;
-            eng.setup(cc, n0, n1, n2, hi);
-        }
-        // the data load is issued before the AES rounds so its latency hides behind them
-        W4 *p = reinterpret_cast<W4 *>(data + 16u * bi);
-        const W4 in = load_block(p);
-        uint32_t k0, k1, k2, k3;
-        eng.block(cc, ctr & 0xffu, k0, k1, k2, k3);
-        const W4 out = {in.x ^ k0, in.y ^ k1, in.z ^ k2, in.w ^ k3};
-        store_block(p, out);
-        const W4 &c = kSeal ? out : in;
-        eng.ghash(z0, z1, z2, z3, gH4);
-        z0 ^= c.x;
-        z1 ^= c.y;
-        z2 ^= c.z;
-        z3 ^= c.w;
-        blast = (int)bi;
+    __device__ __forceinline__ uint32_t aad_len(const Batch &) const { return 13u; }
+    __device__ __forceinline__ void put_tag(uint8_t *data, uint32_t L, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t t3,
+                                            uint32_t, uint32_t, uint32_t, uint32_t prefix) const {
+        dtls_write_tag(data, L, t0, t1, t2, t3, prefix);
     }
-    // One more slot: the partial last block (lane nfull % 4) and E_K(J0) (lane d % 4, the lane
-    // with the fewest data blocks) share one AES pass.
-    const bool part = r && (nfull & 3u) == m;
-    if (part || m == (d & 3u)) {
-        const uint32_t ctr = part ? nfull + 2 : 1u;  // inc32(J0) + nfull, or J0
-        if ((ctr >> 8) != hi) {
-            hi = ctr >> 8;
-            eng.setup(cc, n0, n1, n2, hi);
-        }
-        uint32_t k0, k1, k2, k3;
-        eng.block(cc, ctr & 0xffu, k0, k1, k2, k3);
-        if (part) {
-            uint8_t *blk = data + 16u * nfull;
-            // reads into the tag area (seal: the 16 bytes the tag will take): below L + 16, inside the slot
-            const W4 in = *reinterpret_cast<const W4 *>(blk);
-            const uint32_t q = r >> 2, sb = r & 3u;
-            const uint32_t o0 = in.x ^ k0, o1 = in.y ^ k1, o2 = in.z ^ k2, o3 = in.w ^ k3;
-            uint32_t *bw = reinterpret_cast<uint32_t *>(blk);
-            if (q > 0) bw[0] = o0;
-            if (q > 1) bw[1] = o1;
-            if (q > 2) bw[2] = o2;
-            const uint32_t oq = sel4(q, o0, o1, o2, o3) & lowmask(sb);
-            W4 c = kSeal ? W4{o0, o1, o2, o3} : in;
-            if (kSeal)
-                prefix = oq;  // written with the tag by dtls_write_tag
-            else
-                store_bytes(blk + 4 * q, oq, sb);
-            c.x &= q > 0 ? 0xffffffffu : lowmask(sb);
-            c.y &= q > 1 ? 0xffffffffu : (q == 1 ? lowmask(sb) : 0u);
-            c.z &= q > 2 ? 0xffffffffu : (q == 2 ? lowmask(sb) : 0u);
-            c.w &= q == 3 ? lowmask(sb) : 0u;
-            eng.ghash(z0, z1, z2, z3, gH4);
-            z0 ^= c.x;
-            z1 ^= c.y;
-            z2 ^= c.z;
-            z3 ^= c.w;
-            blast = (int)nfull;
-        } else {
-            e0 = k0;
-            e1 = k1;
-            e2 = k2;
-            e3 = k3;
-        }
+    __device__ __forceinline__ void get_tag(const uint8_t *data, uint32_t L, uint32_t &g0, uint32_t &g1, uint32_t &g2,
+                                            uint32_t &g3) const {
+        dtls_read_tag(data, L, g0, g1, g2, g3);
     }
-    }
-    // Y = sum_m Z_m * H^(e_m)  ^  ([len(A)]||[len(C)]) * H,  e_m = d + 1 - b_last(m) in [2, 5]
-    {
-        const uint32_t em = d + 1u - (uint32_t)blast;
-        const uint32_t tsel = em == 2 ? kGhH2 : em == 3 ? kGhH3 : em == 4 ? kGhH4 : kGhH5;
-        ghash_mul_global(z0, z1, z2, z3, Hg + tsel);
-        uint32_t l0, l1, l2, l3;
-        ghash_lenblock_global(13u, L, Hg, l0, l1, l2, l3);
-        z0 = quad_xor(z0) ^ l0;
-        z1 = quad_xor(z1) ^ l1;
-        z2 = quad_xor(z2) ^ l2;
-        z3 = quad_xor(z3) ^ l3;
-    }
-    e0 = quad_xor(e0);
-    e1 = quad_xor(e1);
-    e2 = quad_xor(e2);
-    e3 = quad_xor(e3);
-    const uint32_t t0 = z0 ^ e0, t1 = z1 ^ e1, t2 = z2 ^ e2, t3 = z3 ^ e3;
-    // the lane owning the partial block (or lane 0) writes the tag
-    const uint32_t owner = r ? (nfull & 3u) : 0u;
-    if (kSeal) {
-        if (m == owner) {
-            dtls_write_tag(data, L, t0, t1, t2, t3, prefix);
-            b.status[pkt] = 1;
-        }
-    } else {
-        uint32_t g0, g1, g2, g3;
-        dtls_read_tag(data, L, g0, g1, g2, g3);  // the tag is never written by Open
-        const bool ok = ((t0 ^ g0) | (t1 ^ g1) | (t2 ^ g2) | (t3 ^ g3)) == 0;
-        if (!ok) {
-            // as qgcm_open_batch: zero the would-be plaintext on a tag mismatch
-            for (uint32_t bi = m; bi < nfull; bi += 4) {
-                const W4 zz = {0, 0, 0, 0};
-                *reinterpret_cast<W4 *>(data + 16u * bi) = zz;
-            }
-            if (r && m == owner) {
-                uint32_t *bw = reinterpret_cast<uint32_t *>(data + 16u * nfull);
-                for (uint32_t w = 0; w < (r >> 2); ++w) bw[w] = 0;
-                store_bytes(data + 16u * nfull + (r & ~3u), 0, r & 3u);
-            }
-        }
-        if (m == 0) b.status[pkt] = ok ? 1 : 0;
-    }
-}
+};
 
 // What the DTLS launch reads beside the Batch: the packets' sessions (checked by the launch that wrote the
 // descriptors), the session table and the header entries.
@@ -1157,8 +1067,6 @@ struct DtlsArgs {
     const DtlsSession *sessions;
     const qgcm_dtls_hdr *hdr;
 };
-
-constexpr uint32_t kDtlsLds = kTeBytes + (uint32_t)quad_waves<true>() * kGhBytes;  // Te, then a comb per wave
 
 template <bool kSeal>
 __global__ void __launch_bounds__(quad_waves<true>() * 64) __attribute__((amdgpu_waves_per_eu(quad_wpe<true>(),
@@ -1223,7 +1131,7 @@ gcm_dtls_kernel(Batch b, const uint32_t *__restrict__ rk_table, DtlsArgs a) {
         const DtlsSession *ss = a.sessions + a.peer[pkt];
         const uint32_t iv = kSeal ? ss->write_iv : ss->read_iv;
         const Keys kk = {rk_table + (size_t)wkey * kRkWords, rk_table + (size_t)wkey * kRkWords + 64};
-        dtls_packet<kSeal>(b, Tab2{kk, {lb, m8}}, pkt, off, L, wkey, m, gH4, iv, a.hdr + pkt);
+        quad_packet<kSeal>(b, Tab2{kk, {lb, m8}}, pkt, off, L, wkey, m, gH4, DtlsFrame{iv, a.hdr + pkt});
     }
 }
 
@@ -2403,60 +2311,37 @@ static int variant_slot(int v) {
 
 static const void *nonce_kernel_of(NonceDest dest);  // the nonce generator's kernels, at the end of the file
 
+// Absolute LDS addressing from 0 requires that a kernel own no static LDS; then its dynamic size is set.
+static hipError_t prepare(const void *kernel, uint32_t lds) {
+    hipFuncAttributes a;
+    const hipError_t e = hipFuncGetAttributes(&a, kernel);
+    if (e != hipSuccess) return e;
+    if (a.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+}
+
 hipError_t init_kernels() {
     g_variants[0] = Variant{reinterpret_cast<const void *>(&gcm_quad_kernel<true, false>),
-                                          reinterpret_cast<const void *>(&gcm_quad_kernel<false, false>),
-                                          quad_waves<false>(), kG5Bytes + kTeBytes + 16u,
-                                          quad_wpe<false>() * 4 / quad_waves<false>(), false, -1};
+                            reinterpret_cast<const void *>(&gcm_quad_kernel<false, false>), quad_waves<false>(),
+                            kG5Bytes + kTeBytes + 16u, quad_wpe<false>() * 4 / quad_waves<false>(), false, -1};
     g_variants[1] = Variant{reinterpret_cast<const void *>(&gcm_quad_kernel<true, true>),
-                                           reinterpret_cast<const void *>(&gcm_quad_kernel<false, true>),
-                                           quad_waves<true>(), kTeBytes + (uint32_t)quad_waves<true>() * kGhBytes,
-                                           1, true, -1};
+                            reinterpret_cast<const void *>(&gcm_quad_kernel<false, true>), quad_waves<true>(),
+                            kDescLds, 1, true, -1};
     g_variants[2] = Variant{reinterpret_cast<const void *>(&gcm_seg_kernel<true>),
-                                           reinterpret_cast<const void *>(&gcm_seg_kernel<false>), 16, kSegLds, 2, true,
-                                           kVariantDescWave};
+                            reinterpret_cast<const void *>(&gcm_seg_kernel<false>), 16, kSegLds, 2, true, kVariantDescWave};
+    hipError_t e = hipSuccess;
     for (const Variant &v : g_variants) {
-        if (!v.seal) continue;
-        for (const void *k : {v.seal, v.open}) {
-            hipFuncAttributes a;
-            hipError_t e = hipFuncGetAttributes(&a, k);
-            if (e != hipSuccess) return e;
-            // absolute LDS addressing from 0 requires no static LDS in the packet kernels
-            if (a.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
-            e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, v.lds);
-            if (e != hipSuccess) return e;
-        }
+        if (e == hipSuccess) e = prepare(v.seal, v.lds);
+        if (e == hipSuccess) e = prepare(v.open, v.lds);
     }
-    for (const void *k : {reinterpret_cast<const void *>(&gcm_one_kernel<true>),
-                          reinterpret_cast<const void *>(&gcm_one_kernel<false>),
-                          reinterpret_cast<const void *>(&gcm_resident_kernel)}) {
-        hipFuncAttributes a;
-        hipError_t e = hipFuncGetAttributes(&a, k);
-        if (e != hipSuccess) return e;
-        if (a.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                k == reinterpret_cast<const void *>(&gcm_resident_kernel) ? kResLds : kOneLds);
-        if (e != hipSuccess) return e;
-    }
-    for (const void *k : {reinterpret_cast<const void *>(&gcm_dtls_kernel<true>),
-                          reinterpret_cast<const void *>(&gcm_dtls_kernel<false>)}) {
-        hipFuncAttributes a;
-        hipError_t e = hipFuncGetAttributes(&a, k);
-        if (e != hipSuccess) return e;
-        if (a.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kDtlsLds);
-        if (e != hipSuccess) return e;
-    }
-    for (NonceDest d : {kNonceArray, kNonceUniform, kNonceDescs}) {  // T-tables at LDS 0, as above
-        const void *k = nonce_kernel_of(d);
-        hipFuncAttributes a;
-        hipError_t e = hipFuncGetAttributes(&a, k);
-        if (e != hipSuccess) return e;
-        if (a.sharedSizeBytes != 0) return hipErrorInvalidKernelFile;
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kTeBytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    if (e == hipSuccess) e = prepare(reinterpret_cast<const void *>(&gcm_one_kernel<true>), kOneLds);
+    if (e == hipSuccess) e = prepare(reinterpret_cast<const void *>(&gcm_one_kernel<false>), kOneLds);
+    if (e == hipSuccess) e = prepare(reinterpret_cast<const void *>(&gcm_resident_kernel), kResLds);
+    if (e == hipSuccess) e = prepare(reinterpret_cast<const void *>(&gcm_dtls_kernel<true>), kDescLds);
+    if (e == hipSuccess) e = prepare(reinterpret_cast<const void *>(&gcm_dtls_kernel<false>), kDescLds);
+    for (NonceDest d : {kNonceArray, kNonceUniform, kNonceDescs})  // T-tables at LDS 0, as the packet kernels'
+        if (e == hipSuccess) e = prepare(nonce_kernel_of(d), kTeBytes);
+    return e;
 }
 
 bool quad_pool_global() { return QGCM_TILE_POOL == 4; }
@@ -2481,7 +2366,7 @@ hipError_t launch_dtls_packets(bool seal, const Batch &b, const uint32_t *d_peer
     void *args[] = {const_cast<Batch *>(&b), const_cast<uint32_t **>(&b.rk_table), &a};
     const void *k = seal ? reinterpret_cast<const void *>(&gcm_dtls_kernel<true>)
                          : reinterpret_cast<const void *>(&gcm_dtls_kernel<false>);
-    return hipLaunchKernel(k, dim3(grid), dim3(quad_waves<true>() * 64), args, kDtlsLds, s);
+    return hipLaunchKernel(k, dim3(grid), dim3(quad_waves<true>() * 64), args, kDescLds, s);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -537,6 +537,32 @@ int run_descs(qgcm_ctx *ctx, bool seal, uint8_t *arena, const qgcm_desc *descs, 
     return rc;
 }
 
+// The sorted worklist of n descriptors (ws_mu held): grows the context's workspace to fit, enqueues the build on
+// s and points b at the result.  status: as for launch_quad_worklist.
+int build_worklist(qgcm_ctx *ctx, bool seal, const qgcm_desc *descs, uint32_t n, hipStream_t s, uint8_t *status,
+                   Batch &b, QuadWorklist &q) {
+    uint32_t items = 0;
+    const size_t need = quad_worklist_bytes(n, ctx->max_keys, &items);
+    if (need > ctx->qws_cap) {
+        if (ctx->d_qws) hipFree(ctx->d_qws);
+        ctx->d_qws = nullptr;
+        ctx->qws_cap = 0;
+        if (hipMalloc(&ctx->d_qws, need) != hipSuccess) return QGCM_E_NOMEM;
+        ctx->qws_cap = need;
+    }
+    if (launch_quad_worklist(descs, n, ctx->max_keys, ctx->d_key_valid, seal, ctx->d_qws, ctx->qws_cap, &q, s, status,
+                             small_worklist(n, ctx->small_wl)) != hipSuccess)
+        return QGCM_E_HIP;
+    b.worklist = q.worklist;
+    b.tile_keys = q.tile_keys;
+    b.runs = q.runs;
+    b.run_next = q.run_next;
+    b.nruns = q.nruns;
+    b.tile_counter = q.tile_counter;
+    b.n_items = q.n_items;
+    return QGCM_OK;
+}
+
 int run_descs_locked(qgcm_ctx *ctx, bool seal, const qgcm_desc *descs, uint32_t n, hipStream_t s, Batch b,
                      uint8_t *arena, const uint8_t *nonces, uint32_t aad_len, uint8_t *status) {
     b.arena = arena;
@@ -558,26 +584,9 @@ int run_descs_locked(qgcm_ctx *ctx, bool seal, const qgcm_desc *descs, uint32_t 
         return QGCM_OK;
     }
     {
-        uint32_t items = 0;
-        const size_t need = quad_worklist_bytes(n, ctx->max_keys, &items);
-        if (need > ctx->qws_cap) {
-            if (ctx->d_qws) hipFree(ctx->d_qws);
-            ctx->d_qws = nullptr;
-            ctx->qws_cap = 0;
-            if (hipMalloc(&ctx->d_qws, need) != hipSuccess) return QGCM_E_NOMEM;
-            ctx->qws_cap = need;
-        }
         QuadWorklist q{};
-        if (launch_quad_worklist(descs, n, ctx->max_keys, ctx->d_key_valid, seal, ctx->d_qws, ctx->qws_cap, &q, s,
-                                 status, small_worklist(n, ctx->small_wl)) != hipSuccess)
-            return QGCM_E_HIP;
-        b.worklist = q.worklist;
-        b.tile_keys = q.tile_keys;
-        b.runs = q.runs;
-        b.run_next = q.run_next;
-        b.nruns = q.nruns;
-        b.tile_counter = q.tile_counter;
-        b.n_items = q.n_items;
+        const int rc = build_worklist(ctx, seal, descs, n, s, status, b, q);
+        if (rc != QGCM_OK) return rc;
         // a key is a run once it has kSegMinTiles tiles, i.e. (kSegMinTiles - 1) * 16 + 1 packets (the
         // worklist's ceil(count / 16)); a smaller batch cannot give any key a run, so only the segmented
         // kernel's complement (the per-wave kernel) is launched
@@ -2018,15 +2027,6 @@ int dtls_run(qgcm_ctx *ctx, bool seal, uint8_t *arena, uint64_t stride, uint32_t
         if (hipMalloc(&ctx->d_dtls_work, need) != hipSuccess) return QGCM_E_NOMEM;
         ctx->dtls_work_cap = need;
     }
-    uint32_t items = 0;
-    const size_t qneed = quad_worklist_bytes(n, ctx->max_keys, &items);
-    if (qneed > ctx->qws_cap) {
-        if (ctx->d_qws) hipFree(ctx->d_qws);
-        ctx->d_qws = nullptr;
-        ctx->qws_cap = 0;
-        if (hipMalloc(&ctx->d_qws, qneed) != hipSuccess) return QGCM_E_NOMEM;
-        ctx->qws_cap = qneed;
-    }
     DtlsCall c{};
     c.stride = stride;
     c.n = n;
@@ -2048,13 +2048,8 @@ int dtls_run(qgcm_ctx *ctx, bool seal, uint8_t *arena, uint64_t stride, uint32_t
     b.n = n;
     QuadWorklist q{};
     // (no status array: the launches above have written every packet's)
-    if (launch_quad_worklist(b.descs, n, ctx->max_keys, ctx->d_key_valid, seal, ctx->d_qws, ctx->qws_cap, &q, s, nullptr,
-                             small_worklist(n, ctx->small_wl)) != hipSuccess)
-        return QGCM_E_HIP;
-    b.worklist = q.worklist;
-    b.tile_keys = q.tile_keys;
-    b.tile_counter = q.tile_counter;
-    b.n_items = q.n_items;
+    const int rc = build_worklist(ctx, seal, b.descs, n, s, nullptr, b, q);
+    if (rc != QGCM_OK) return rc;
     const uint32_t tiles = (b.n_items + 15) / 16, waves = (uint32_t)dtls_waves();
     const uint32_t cus = (uint32_t)std::max(1, ctx->num_cus - resident_workers_running(ctx->res.load(std::memory_order_acquire)));
     const uint32_t wgs = std::max(1u, (tiles + waves - 1) / waves);

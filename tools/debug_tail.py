@@ -1,4 +1,4 @@
-"""Debug probe for the in-slot nonce/tag path (read_tail/write_tail) at every L % 4."""
+"""Debug probe for the in-slot nonce/tag path (read_nonce, read_tag, write_tail) at every L % 4."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
